@@ -5,8 +5,9 @@ nx = ny = 4096, nt = 201 as ONE PDHG window of T = nt - 1 = 200 unknown time row
 (time_step_per_PDHG = nt), rho_alp_iters = 1 (the fused-sweep headline),
 fp64 state resident in HBM -- the reference's arithmetic (jaxsrc/update_fns_in_pdhg.py:10), the one that meets
 north_star's 1e-5 at this config's epsl = 0.1 -- reference initial state (phi = g, rho = 70, alp = 0;
-utils_pdhg_solver.py:123-137).  The same workload in fp32 is reported nested ("fp32_precision") as a throughput
-reference: fp32 does not meet the 1e-5 bar at epsl = 0.1.  One "step" = one outer PDHG iteration
+utils_pdhg_solver.py:123-137).  With --full the same workload in fp32 is reported nested ("fp32_precision") as a
+throughput reference: fp32 does not meet the 1e-5 bar at epsl = 0.1.
+One "step" = one outer PDHG iteration
 (utils_pdhg_solver.py:51-88): primal (residual + H1 preconditioner + update), extrapolation,
 dual (alpha/rho prox), err1/err2 and the device-side stop tests.
 
@@ -19,6 +20,18 @@ scaling is "strong"; value = iterations of the window / max-over-ranks time.
 grid): the window's x rows split into N x-slabs (pdhg_amd/xslab.py): halo-row
 allgathers and two all-to-all transposes of the spectrum per iteration.  At N = 1 it runs one x-slab
 through the same phases (LocalComm), so its line measures the decomposition's overhead.
+
+A plain run (no --full) does only what the headline figure needs: context, W warm-up iterations, the K timed
+iterations (with their live per-class HIP events), the --dump-outputs files if asked for, and the result line.
+--full adds everything that takes runs of its own: the rocprofv3 PMC traffic passes, the nested line in the other
+precision, the non-finite probe with its finite segment, and the CPU baseline (each can still be left out of a
+--full run with its --no-* option).
+
+--dump-outputs DIR (single-GPU context): after the timed iterations, what a caller of the timed path holds --
+the stop statistics pdhg_iterate returned for the K timed iterations (stats.npy) and the state phi, rho and
+the controls alp0.. as get_rows returns them (float64) -- is written as DIR/<name>.npy.  Windows too large to
+dump whole are sampled: DUMP_ROWS time rows spread evenly over the window, and of each row the same DUMP_POINTS
+grid points drawn once with a fixed seed, so two builds run with the same arguments write comparable files.
 """
 import argparse
 import json
@@ -63,6 +76,47 @@ def grid(ndim, nx, ny):
     if ndim == 1:
         return x1, None
     return x1, np.linspace(0.0, 2.0, num=ny, endpoint=False)
+
+
+DUMP_ROWS = 3          # time rows dumped of a window with more rows (first, middle, last)
+DUMP_POINTS = 65536    # grid points dumped of a row with more points (fixed seeded sample)
+DUMP_SEED = 20240607
+STAT_KEYS = ("iters_run", "status", "inner_last", "inner_total", "err1", "err2", "err_inner", "nan_seen",
+             "first_nan_iter")
+
+
+def dump_sample(n_rows, n_points):
+    """(time rows, flat grid-point indices or None for the whole row) of --dump-outputs for an array of n_rows
+    rows of n_points points: the same for every run of the same window."""
+    rows = np.unique(np.linspace(0, n_rows - 1, min(n_rows, DUMP_ROWS)).round().astype(np.int64))
+    if n_points <= DUMP_POINTS:
+        return rows, None
+    return rows, np.sort(np.random.default_rng(DUMP_SEED).choice(n_points, DUMP_POINTS, replace=False))
+
+
+def dump_outputs(ctx, st, out_dir):
+    """--dump-outputs: the timed path's results after its last step (module docstring), one row at a time so the
+    host never holds more than one row of the window."""
+    os.makedirs(out_dir, exist_ok=True)
+    npts = int(np.prod(ctx._space))
+    rows_phi, idx = dump_sample(ctx.T + 1, npts)
+    rows_dual, _ = dump_sample(ctx.T, npts)
+
+    def pick(a, trailing=()):
+        a = a.reshape((npts,) + trailing)
+        return a if idx is None else a[idx]
+
+    phi = [pick(ctx.get_rows(int(r), 1, phi=True, rho=False, alp=False)[0]) for r in rows_phi]
+    rho, alp = [], [[] for _ in range(ctx.n_alp)]
+    for r in rows_dual:
+        _, _, rh, al = ctx.get_rows(int(r), 1, phi=False, rho=True, alp=True)
+        rho.append(pick(rh))
+        for i, a in enumerate(al):
+            alp[i].append(pick(a, (ctx.n_ctrl,)))
+    arrays = {"stats": np.array([float(st[key]) for key in STAT_KEYS]), "phi": np.stack(phi), "rho": np.stack(rho)}
+    arrays.update({"alp{}".format(i): np.stack(a) for i, a in enumerate(alp)})
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(cfg, T_sample, threads, reps_min=3):
@@ -139,8 +193,7 @@ def pmc_traffic(args):
         cmd = [prof, "--pmc", ctr, "--output-format", "csv", "-d", d, "-o", "run", "--",
                sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", str(PMC_ITERS - 1),
                "--warmup", "1",
-               "--rho-alp-iters", str(args.rho_alp_iters), "--precision", args.precision, "--no-cpu-baseline",
-               "--no-pmc", "--no-probe", "--no-reference-precision"]
+               "--rho-alp-iters", str(args.rho_alp_iters), "--precision", args.precision]   # a plain run
         try:
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600,
                            env=dict(os.environ, TMPDIR="/tmp"))
@@ -298,7 +351,7 @@ def other_precision_run(args, prec):
     progress("nested {} run (child process)".format(prec))
     cmd = [sys.executable, os.path.abspath(__file__), "--config", args.config, "--steps", str(args.steps),
            "--warmup", str(args.warmup), "--rho-alp-iters", str(args.rho_alp_iters), "--precision", prec,
-           "--no-cpu-baseline", "--no-reference-precision"]
+           "--full", "--no-cpu-baseline", "--no-reference-precision"]
     if args.no_pmc:
         cmd.append("--no-pmc")
     try:
@@ -404,6 +457,12 @@ def main():
     ap.add_argument("--precision", default=None, choices=["fp32", "fp64"],
                     help="fp64 (default: the reference's arithmetic, the one that meets the parity bar at epsl 0.1; "
                          "also the marching stop counts are only the reference's in it) or fp32")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes runs of its own: the rocprofv3 PMC traffic passes, the nested line in "
+                         "the other precision, the non-finite probe with its finite segment and the CPU baseline "
+                         "(the --no-* options below leave single ones out of a --full run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's results after its last step as DIR/<name>.npy (single-GPU context)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample-T", type=int, default=1)
     ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 PMC traffic passes")
@@ -422,6 +481,14 @@ def main():
     args = ap.parse_args()
     if args.precision is None:
         args.precision = "fp64"
+    if args.dump_outputs and ((args.gpus or 1) > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1
+                              or args.decomp != "tslab" or args.marching or args.selftest):
+        ap.error("--dump-outputs writes the single-GPU context's state (--gpus 1, --decomp tslab, no --marching)")
+    # a plain run times the window and nothing else; the extra legs belong to --full
+    do_pmc = args.full and not args.no_pmc
+    do_probe = args.full and not args.no_probe
+    do_other_precision = args.full and not args.no_reference_precision
+    do_cpu_baseline = args.full and not args.no_cpu_baseline
 
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -463,10 +530,10 @@ def main():
         return marching(args)
 
     pmc, pmc_err = None, "disabled"
-    if world == 1 and not args.no_pmc and args.decomp == "tslab":
+    if world == 1 and do_pmc and args.decomp == "tslab":
         pmc, pmc_err = pmc_traffic(args)   # before this process initialises the GPU
     other_prec = None
-    if world == 1 and args.decomp == "tslab" and not args.no_reference_precision:
+    if world == 1 and args.decomp == "tslab" and do_other_precision:
         # likewise before this process initialises the GPU
         other_prec = other_precision_run(args, "fp32" if args.precision == "fp64" else "fp64")
 
@@ -554,7 +621,7 @@ def main():
     first_nonfinite = None
     probe_n = 0
     progress("context ready")
-    if not args.no_probe:
+    if do_probe:
         init()
         ctx.set_stop_rules(converge=True, nan=True)
         probe_n = max(args.warmup + args.steps, 20)
@@ -602,7 +669,7 @@ def main():
     # finite segment: iterations 2..F from the reference state (the first, untimed, forms its residual from
     # scratch), all before the first non-finite one
     finite = None
-    if not args.no_probe:
+    if do_probe:
         F = 10 if first_nonfinite is None else min(10, first_nonfinite - 1)
         if F >= 2:
             init()
@@ -626,6 +693,9 @@ def main():
     exch = runner.exchange_times() if runner is not None else None
     if runner is not None:
         runner.timing = False
+    if args.dump_outputs:
+        progress("dump outputs")
+        dump_outputs(ctx, st, args.dump_outputs)
     el_max = max_over_ranks(el)
     iters = st["iters_run"]
     iters_total = iters          # one window: every rank ran the same iterations
@@ -716,7 +786,7 @@ def main():
     out["parity"] = PARITY[args.precision]
     if other_prec is not None:
         out["reference_precision" if args.precision == "fp32" else "fp32_precision"] = other_prec
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and do_cpu_baseline:
         threads = min(16, os.cpu_count() or 1)
         sample_cfg = CONFIGS[args.config]
         progress("cpu baseline (float64 oracle, bounded sample)")

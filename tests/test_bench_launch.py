@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -36,6 +38,69 @@ def test_gpus_mismatch_with_launcher_env_fails():
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--selftest"], env=env,
                        capture_output=True, text=True, timeout=120)
     assert p.returncode != 0 and "WORLD_SIZE=1" in (p.stderr + p.stdout)
+
+
+def test_dump_sample_is_fixed_and_bounded():
+    """--dump-outputs samples a large window the same way in every run (two builds are compared file for file) and
+    keeps the whole dump of the largest config far below 64 MB; small windows are dumped whole."""
+    sys.path.insert(0, ROOT)
+    import bench
+    rows, idx = bench.dump_sample(201, 4096 * 4096)
+    rows2, idx2 = bench.dump_sample(201, 4096 * 4096)
+    assert rows.tolist() == [0, 100, 200] and (idx == idx2).all() and (rows == rows2).all()
+    assert len(idx) == bench.DUMP_POINTS and len(set(idx.tolist())) == len(idx)
+    assert idx.min() >= 0 and idx.max() < 4096 * 4096 and (idx[1:] > idx[:-1]).all()
+    rows, idx = bench.dump_sample(2, 160)
+    assert rows.tolist() == [0, 1] and idx is None
+    assert bench.dump_sample(1, 160)[0].tolist() == [0]
+    # phi, rho and 4 controls of 2 components, float64, of the sampled rows
+    assert bench.DUMP_ROWS * bench.DUMP_POINTS * 8 * (1 + 1 + 4 * 2) < 64e6
+
+
+def test_dump_outputs_needs_the_single_gpu_context(tmp_path):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dump-outputs",
+                        str(tmp_path / "d")], capture_output=True, text=True, timeout=120)
+    assert p.returncode != 0 and "--dump-outputs" in p.stderr and not (tmp_path / "d").exists()
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_state_it_ends_in(native, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` line carries the headline figures and none of the --full
+    legs, and --dump-outputs writes the state after W + K iterations from the reference initial state: compared
+    with the same iterations through a context of this process (the same kernels on the same inputs: equal)."""
+    import numpy as np
+    import bench
+    from pdhg_amd.context import PDHGContext
+    d = tmp_path / "dump"
+    out = _run(["--gpus", "1", "--steps", "3", "--warmup", "2", "--config", "c0", "--dump-outputs", str(d)])
+    assert out["steps"] == 3 and out["warmup"] == 2 and out["config"]["iters_executed"] == 3
+    assert out["unit"] == "it/s" and out["dtype"] == "f64" and out["higher_is_better"] is True
+    assert abs(out["ms_per_step"] * out["value"] - 1e3) < 1e-6 * 1e3
+    for key in ("cpu_baseline", "fp32_precision", "reference_precision", "finite_segment", "pmc_by_kernel"):
+        assert key not in out
+    assert out["config"]["first_nonfinite_iter"] is None and out["config"]["nonfinite_probe_iters"] == 0
+
+    egno, ndim, epsl, nx, ny, nt = bench.CONFIGS["c0"]
+    T = nt - 1
+    xs, _ = bench.grid(ndim, nx, ny)
+    ctx = PDHGContext(egno, ndim, nx, ny, T, 2.0 / nx, 0.0, 1.0 / T, xs, None, epsl=epsl, precision="fp64",
+                      rho_alp_iters=1, device=0)
+    ctx.init_state(np.sin(np.pi * xs))
+    ctx.set_stop_rules(converge=True, nan=False)
+    ctx.iterate(2, 0.1 / 1.5, 0.1 * 1.5, 1e-6, 1)
+    st = ctx.iterate(3, 0.1 / 1.5, 0.1 * 1.5, 1e-6, 1)
+    phi, rho, alp = ctx.get_state()
+    ctx.close()
+    rows_phi, idx = bench.dump_sample(T + 1, nx)
+    rows_dual, _ = bench.dump_sample(T, nx)
+    assert idx is None
+    got = {f[:-4]: np.load(str(d / f)) for f in sorted(os.listdir(str(d)))}
+    assert sorted(got) == ["alp0", "alp1", "phi", "rho", "stats"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["phi"], phi[rows_phi]) and np.array_equal(got["rho"], rho[rows_dual])
+    assert np.array_equal(got["alp0"], alp[0][rows_dual]) and np.array_equal(got["alp1"], alp[1][rows_dual])
+    assert np.array_equal(got["stats"], np.array([float(st[k]) for k in bench.STAT_KEYS]))
+    assert np.isfinite(got["phi"]).all() and np.abs(got["rho"] - 70.0).max() > 0.0   # the state moved
 
 
 def _scale_worker(rank, world, port, out_path):
