@@ -172,6 +172,11 @@ int pdhg_device_bytes(pdhg_ctx* ctx, unsigned long long* bytes);
  * windows of iterations from a captured HIP graph; default on, environment PDHG_GRAPH=0 launches every
  * iteration eagerly), "graph_window" (iterations per replayed graph). */
 int pdhg_path_info(pdhg_ctx* ctx, const char* key, int* value);
+/* The same keys for the single context pdhg_create would build from `prob` under the current environment, without a
+ * device: the problem is validated as in pdhg_create (same status codes) and the kernel paths are planned, nothing is
+ * created.  The runtime counters ("contig_fail", "spec_iters", "spec_halts", "graph", "graph_window") belong to a
+ * context and return PDHG_ERR_ARG here. */
+int pdhg_plan_info(const pdhg_problem* prob, const char* key, int* value);
 
 /* Per-launch kernel timing for the benchmark: HIP events recorded on the
  * context's stream around every launch of the named kernel class

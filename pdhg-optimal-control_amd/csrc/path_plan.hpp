@@ -1,0 +1,468 @@
+// Which kernels a context runs and with what geometry: decided once, at context creation, by plan_paths() -- a pure
+// function of the problem, the precision, the decomposition and the Tuning (no device, no environment).  The
+// launchers (ctx_impl.hpp) read the PathPlan and re-test nothing; pdhg_path_info / pdhg_plan_info answer from it.
+// The decisions are ordered: a later one reads the earlier ones' values (marked "reads" below).
+#pragma once
+
+#include <cstdio>
+#include <string>
+
+#include "../../include/pdhg.h"
+#include "fft_lds.hpp"
+#include "kernels_dual_multi.hpp"
+#include "kernels_fs16.hpp"
+#include "tuning.hpp"
+
+namespace pdhg {
+
+constexpr size_t kLdsBytes = 160 * 1024;
+constexpr int kMultiSub = 5;    // sub-iterations one chunk pass of the dual loop runs (kernels_dual_multi.hpp)
+constexpr int kFoldRows = 64;   // rows of the first fold level (k_fold_partials) after the partial table
+
+inline FFTPlan make_plan(int n, bool& ok) {
+  FFTPlan pl{};
+  pl.n = n;
+  pl.pow2 = (n > 0) && ((n & (n - 1)) == 0);
+  int m = n, np = 0;
+  ok = true;
+  auto push = [&](int r) {
+    if (np >= kMaxPass) { ok = false; return; }
+    pl.radix[np++] = r;
+  };
+  for (int r : {16, 8, 4, 2})
+    while (m % r == 0 && m > 1) { push(r); m /= r; }
+  while (m % 3 == 0) { push(3); m /= 3; }
+  for (int f = 5; m > 1; f += 2)
+    while (m % f == 0) { push(f); m /= f; }
+  pl.npass = np;
+  return pl;
+}
+
+// single context, or one part of a multi-GPU decomposition
+struct Decomp {
+  bool slab = false;    // t-slab: this context owns unknown rows [j0, j0 + T) of a window of Tg
+  int j0 = 0, Tg = 0;
+  bool xslab = false;   // x-slab: global x rows [rank * nloc, (rank + 1) * nloc) of nxg; pb.nx = nloc + 16 local rows
+  int rank = 0, P = 1, nxg = 0, nloc = 0;
+};
+
+struct PathPlan {
+  FFTPlan plx{}, ply{};   // x (global length) and y line transforms
+  int na = 0, n_dead = 0;
+  bool two_sets = false;  // rho_alp_iters > 1: two (rho, alp) buffer sets
+  // spectral blocks (KP::B / lB / nb / half_real / tile_j)
+  int B = 1, lB = 0, nb = 1, tile_j = 0;
+  bool half_real = false;         // 2-D nx = 8192: one real column per x-transform block
+  int xs_nbs = 0;                 // x-slab: column blocks of this rank
+  // launch geometry
+  int NT2 = 512;
+  int gx1 = 0, gx4 = 0, g4 = 1, gx5 = 0, g5 = 1, g_outer = 1;
+  int head_xrun = 4;              // x rows per workgroup of the head form's chunk passes
+  int nt_row = 256;               // threads of the generic 2-D row kernels (k_res_fwdy_2d, k_invy_update_2d)
+  int rows_var = 0;               // row-kernel shape variant (with_fast_rows)
+  int res64_nt = 512;             // fp64 fused residual threads at ny = 4096
+  int half_nt = 3;                // ny = 4096 row kernels with 512 threads (bit 0 residual, bit 1 update)
+  int upd_pf = 4;                 // update kernel (512 threads): old-phi row pairs in flight (1..4)
+  int NTd = 256, gxd = 0, gyd = 0, gzd = 0, jchunk_d = 1;
+  int gz_1d = 1, jchunk_1d = 1;   // 1-D fused residual (k_dual_1d_fr): time chunks of the dual sweep
+  int nt1d = 256;                 // 1-D residual / update block size (1024 on the global-scratch path)
+  int RWf = 8, NTf = 1024, g_fast_upd = 1;   // fast row kernels: rows per workgroup, threads, update grid
+  size_t partial_rows = 0;
+  // LDS bytes
+  size_t lds_res = 0, lds_xt = 0, lds_batch_xt = 0, lds_fast_xt = 0, lds_fast = 0, lds_fast_tw = 0, lds_res64 = 0,
+         lds_upd64 = 0;
+  // dual
+  bool fast_dual = false;         // row-per-thread / LDS-row time-marching dual instead of the per-point kernel
+  int dual_rx = 0;                // > 0: k_dual_lds_2d with dual_rx x rows per workgroup (x neighbours through LDS)
+  int dual_ypl = 4;               // y per lane of k_dual_lds_2d (fp64: 4 or 2)
+  int dual_one = 0;               // as launched: k_dual_fast_2d<.., ONE> on one-row workgroups (0: marching form)
+  bool dual_multi = false;        // rho_alp_iters > 1: the dual loop in chunks of sub-iterations
+  bool dual_head = false;         // ... below 2^25 points: sub-iteration 0 alone, the rest in chunks
+  bool k1_outer = true;           // one-sub-iteration loops skip the outer-sum pass
+  bool fold_fin = false;          // fold + finalize of a folded partial table in one launch
+  bool spec_ok = false;           // iterate() may use the speculative one-sub-iteration schedule (head form)
+  bool fin_merge = true;          // ... with its dual and outer finalizes in one launch
+  // fused residual: the dual sweep also forms the next primal's residual rows (k_dual_lds_2d FR / k_dual_1d_fr), the
+  // residual kernel only completes the tile-edge terms and transforms
+  bool fuse_res = false;
+  // row kernels
+  bool fast_rows = false;         // fp32, power-of-two ny: RWf rows per workgroup, NTf threads
+  bool res64 = false;             // fp64 residual and update through the fast row kernels (4-row groups)
+  bool ip_rows = false;           // fp64 ny = 8192: generic row kernels on one padded in-place line (FFTIp)
+  bool upd8192 = false;           // fp64 ny = 8192, half-real x: update through the fast row kernel on 2-row tasks
+  bool tc_spec = false;           // fp64 C3: residual spectrum in task order (KP::rspec)
+  bool to_c4 = false;             // C4 (half-real x blocks): fused residual in task order + transpose
+  int res_threads = 0, upd_threads = 0;   // as launched: fast row kernels' threads after half_nt (0: not the fast rows)
+  int res64_nt2048 = 512;         // fp64 unfused residual's threads at ny = 2048
+  int upd_t1 = 0;                 // fp64 ny = 2048 update on one-row windows: 256 threads + G16 seeds (2: PF 2, 1: PF 4)
+  // x transform
+  bool t1_xt = true;              // T = 1 windows: carry-free x transform (k_precond_x_t1_2d)
+  bool fast_xt = false;           // fp32 power-of-two nx: the fast x kernels ...
+  int fast_xt_code = 0;           // ... as launched: 1 single-role, 2 warp-specialised, 3 batched, 4 DMA, 5 DMA half-real
+  bool xt_dma = false, xt_pair = false;   // the batched kernel's nx = 4096 forms
+  int xt_rpre = 0;
+  bool t1_xt64 = false;           // fp64 T = 1 windows: k_precond_x_t1_2d<..., double>
+  bool t1_g16 = false;            // as launched: ... with the later passes' twiddle seeds from global memory
+  bool f64_xt = false;            // fp64: in-place line + register carries (k_precond_xt_f64_2d)
+  int xt64_var = 0;               // nx = 2048 shape of it (threads, b' in registers or LDS)
+  // 1-D
+  bool glb_line = false;          // line FFTs over global scratch (nx beyond LDS)
+  bool fourstep = false;          // nx = 65536: four-step DHT
+  bool fs_wide = true;            // ... with 64-column / 32-row tiles (k_fs1w_1d / k_fs2w_1d)
+  bool fs16 = false;              // ... as a 16 x 4096 split with a chunk-major spectrum (kernels_fs16.hpp)
+  int f16_group = 16;             // rows n1 per load group of k_f16a_fwd_1d
+  bool thomas_chunk = false;      // t-solve in chunks of rows (k_thomas_chunk_1d)
+};
+
+// S = sizeof(real) (4 / 8).  pb is the context's own problem (an x-slab's has its local rows).  Returns PDHG_OK, or
+// PDHG_ERR_UNSUPPORTED with the reason in err.
+inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tuning& tn, PathPlan& pl,
+                      std::string& err) {
+  auto fail = [&err](int code, const char* fmt, auto... args) {
+    if constexpr (sizeof...(args) == 0) {
+      err = fmt;
+    } else {
+      char buf[512];
+      snprintf(buf, sizeof(buf), fmt, args...);
+      err = buf;
+    }
+    return code;
+  };
+  pl = PathPlan{};
+  const int nx = pb.nx, ny = pb.ny, T = pb.T;
+  const int nxg = dc.xslab ? dc.nxg : nx;   // length of the x transform (global nx for an x-slab)
+  const bool is2d = pb.ndim == 2, slab = dc.slab, xslab = dc.xslab;
+  const size_t csz = 2 * (size_t)S;
+  pl.na = (pb.ndim == 1 || pb.egno == 3) ? 2 : 4;
+  pl.n_dead = (pb.ndim == 2 && pb.egno == 3) ? 2 : 0;
+  const bool two_sets = pl.two_sets = pb.rho_alp_iters > 1;
+  bool ok1 = true, ok2 = true;
+  pl.plx = make_plan(nxg, ok1);
+  if (is2d) pl.ply = make_plan(ny, ok2);
+  if (!ok1 || !ok2) return fail(PDHG_ERR_UNSUPPORTED, "FFT plan too deep for nx=%d ny=%d", nxg, ny);
+
+  if (is2d) {
+    // spectral block width B: contiguous [nx][B] slabs; the x-transform workgroup holds
+    // M = nx*B modes with 5*M*sizeof(R) bytes of LDS (FFT ping-pong + Thomas carries)
+    const size_t cap = (S == 4) ? 8192 : 4096;
+    int B = 16;
+    while (B > 2 && (size_t)nxg * B > cap) B >>= 1;
+    int nyp = 2;
+    while (nyp < ny) nyp <<= 1;
+    if (B > nyp) B = nyp;
+    // fp64 nx = 512 / 1024 with T > 1: one column pair per block (B = 2) for the fp64 x kernel below (the generic
+    // kernel would take B = 8 / 4 with its carries in global memory); T = 1 keeps the one-row kernel's B
+    // (a t-slab takes the window's row count, so every slab of one window gets the same layout: a 1-row slab of a
+    // longer window must not keep B = 8 / 4 while its neighbours exchange B = 2 carry planes)
+    const bool xt64_on = tn.xt64.value_or(1) != 0;
+    const bool f64_small = S == 8 && pb.bc_x == 0 && (slab ? dc.Tg : T) > 1 && (nxg == 1024 || nxg == 512) &&
+                           ny % 2 == 0 && xt64_on;
+    if (f64_small) B = 2;
+    // fp32 nx = 8192 (C4): one real column per block, packed into a 4096-point FFT (half_real)
+    // fp64 nx = 8192 (C4's grid in the reference's precision): the same half-real split in k_precond_xt_f64_2d<HR>
+    pl.half_real = nxg == 8192 && pb.bc_x == 0 && (S == 4 || !xslab);
+    if (pl.half_real) B = 1;
+    // fp64 nx = 4096 (C3's grid in the reference's precision): k_precond_xt_f64_2d keeps the carries in
+    // registers, so the column pair (B = 2) fits LDS although 5 M reals would not
+    // (t-slab phases too: kernels_xt_f64.hpp)
+    // fp64 nx = 2048 (C2's grid): the same kernel with b' in registers (BPR) instead of the generic runtime-radix
+    // kernel's global carries (10.97 ms at C2, 0.15 of the HBM roofline, round 4)
+    // (reads B, half_real, f64_small)
+    pl.f64_xt = S == 8 && pb.bc_x == 0 &&
+                (((nxg == 4096 || nxg == 2048) && B == 2) || (nxg == 8192 && pl.half_real) || f64_small) && xt64_on;
+    pl.xt64_var = tn.xt64_var;
+    // fp64 one-row windows at a power-of-two nx: the carry-free transform needs only the padded lines
+    pl.t1_xt64 = S == 8 && T == 1 && pb.bc_x == 0 && !pl.half_real && !slab && pl.plx.pow2 &&
+                 nxg >= 512 && nxg <= 4096 && nxg * (B / 2) == (nxg == 4096 ? 4096 : 2048);
+    // fp64 unfused residual's threads at ny = 2048: 256 on one-row windows (two 4-wave workgroups per CU, 225 VGPRs;
+    // C2's T = 1 residual 54 -> 47 us), 512 otherwise (C2's T = 100 unfused residual 4.66 vs 4.94 ms at 256)
+    pl.res64_nt2048 = tn.res64_nt2048.value_or(T == 1 ? 256 : 512);
+    // steady marching iteration 0.2196 (512 threads) / 0.2150 (PF 4) / 0.2131 ms (PF 2)
+    pl.upd_t1 = T == 1 ? tn.upd_t1.value_or(2) : 0;
+    if (!pl.half_real && !pl.f64_xt && (size_t)nxg * B > cap)
+      return fail(PDHG_ERR_UNSUPPORTED, "nx=%d too large for the x-transform slab (max %zu in this precision)", nxg,
+                  cap / 2);
+    pl.B = B;
+    while ((1 << pl.lB) < B) ++pl.lB;
+    pl.nb = (ny + B - 1) / B;
+    pl.lds_res = 2 * (size_t)ny * csz;
+    const int nmodes = nxg * B;
+    pl.lds_xt = (size_t)5 * nmodes * S;
+    // fp64 ny = 8192 (C4's y extent in the reference's precision): the generic row kernels transform the row pair
+    // in place in one padded line (FFTIp, 136 KiB) instead of a Stockham ping-pong of two (256 KiB)
+    pl.ip_rows = S == 8 && ny == 8192 && pl.lds_res > kLdsBytes && !xslab;
+    if (pl.ip_rows) pl.lds_res = (size_t)Pad<8192>::LINE * csz;
+    // ... and the update through the fast row kernel on 2-row tasks when the x blocks are half-real (B = 1)
+    pl.upd8192 = pl.ip_rows && pl.half_real && nx % 2 == 0 && tn.upd8192.value_or(1) != 0;
+    if (pl.upd8192) pl.g_fast_upd = std::min((nx / 2) * T, 2048);
+    if (pl.lds_res > kLdsBytes) return fail(PDHG_ERR_UNSUPPORTED, "ny=%d exceeds the LDS row transform", ny);
+    {   // generic row kernels: when the LDS admits few workgroups per CU (fp64 ny = 4096: one), wider
+        // workgroups keep >= 16 waves per CU in flight for the residual's scattered loads
+      const int wg = (int)std::max<size_t>(1, kLdsBytes / std::max<size_t>(pl.lds_res, 1));
+      pl.nt_row = std::min(1024, 256 * std::max(1, 4 / wg));
+    }
+    pl.NT2 = std::min(512, ((nmodes + 63) / 64) * 64);
+    pl.gx1 = ((nx + 1) / 2) * T;                      // row-pair tasks (flat grid)
+    pl.gx4 = (int)std::min<long long>((long long)pl.gx1, 4096);
+    pl.gx5 = (ny + 255) / 256;
+    pl.g5 = std::max(1, std::min(T * nx, 8192 / std::max(1, pl.gx5)));
+    pl.t1_xt = tn.t1_xt;
+    pl.k1_outer = tn.k1_outer;
+    pl.fold_fin = tn.fold_fin;
+    // short windows (the reference's T = 1 marching default): few time rows per workgroup leave little to
+    // pipeline over t, so occupancy decides.  Measured on C3's grid (bench --config c3w1/c3w4/c3w8): the
+    // single-role x-transform kernel beats the warp-specialised one up to T = 8 at least (T = 1: 0.18 vs
+    // 0.24 ms, T = 8: 0.79 vs 0.84 ms); the row-per-thread dual (146 VGPRs, 3 waves/SIMD) without the
+    // fused residual beats the fused 8-row sweep (200 VGPRs, 2 waves/SIMD) at T = 1 (0.31 vs 0.41 ms),
+    // ties at T = 4 and loses from T = 8 on.
+    const bool short_win = T < tn.short_t_xt, short_dual = T < tn.short_t_dual;
+    bool ws_xt = false, batch_xt = false, xt_dma_hr = false;
+    if (pl.half_real && S == 4) {
+      pl.fast_xt = true;
+      ws_xt = true;
+      // the LDS-DMA staged x transform on half-real blocks (k_precond_xt_dma_2d<4096, true>) for windows of >= 4
+      // rows: c4w50 x transform 28.4 ms with the warp-specialised kernel (round 4, 1.9 TB/s)
+      xt_dma_hr = tn.xt_dma_hr ? *tn.xt_dma_hr != 0 : T >= 4;
+      pl.lds_fast_xt = (size_t)(2 * (4096 + 4096 / 16) + 816 + 4096) * csz;   // + split twiddles
+    } else if (S == 4 && pl.plx.pow2 && nxg * (B / 2) == 4096 && nxg >= 512 && pb.bc_x == 0) {
+      pl.fast_xt = true;
+      // the other widths spill registers in the warp-specialised form
+      ws_xt = tn.xt_ws ? *tn.xt_ws != 0 : (nxg == 4096) && !short_win;
+      // row-batched x transform (k_precond_xt_batch_2d): 4 rows per transform, 1024 threads.  Measured at C3
+      // (nx = 4096, T = 200): 16.2 -> 14.5 ms against the warp-specialised kernel; at C2 (nx = 2048,
+      // T = 100) 2.07 -> 1.82 ms against the single-role one.  nx = 1024 / 512 spill in it: not selected.
+      batch_xt = tn.xt_batch ? *tn.xt_batch != 0 : (nxg == 4096 || nxg == 2048) && T >= 4;
+      pl.xt_rpre = tn.xt_rpre;
+      pl.xt_pair = tn.xt_pair;
+      // LDS-DMA staged rows (k_precond_xt_dma_2d) at nx = 4096: C3 14.24 -> 13.52 ms
+      pl.xt_dma = nxg == 4096 && tn.xt_dma.value_or(1) != 0;
+      pl.lds_batch_xt = (size_t)(4 * (4096 + 4096 / 16) + twlds_size(nxg)) * csz;
+      // padded FFT buffer + theta, E, b' (float2 per item) + twiddle seeds (TwLds<nx>)
+      pl.lds_fast_xt = ws_xt ? (size_t)(2 * (4096 + 4096 / 16) + 816) * csz
+                             : (size_t)(4096 + 4096 / 16 + 3 * 4096 + 816) * csz;
+    }
+    // (an x-slab reports its local row count here, as pdhg_path_info always has)
+    pl.fast_xt_code = !pl.fast_xt ? 0 : (pl.half_real && xt_dma_hr) ? 5
+                      : (batch_xt && !pl.half_real) ? ((pl.xt_dma && pb.nx == 4096) ? 4 : 3) : ws_xt ? 2 : 1;
+    pl.t1_g16 = pl.t1_xt64 && pl.t1_xt && tn.t1_g16 && (nxg == 2048 || nxg == 4096);
+    // fp64: the row-per-thread time-marching dual (k_dual_fast_2d<EGNO, double>) instead of the generic
+    // per-point kernel, which re-reads every phi_bar neighbour (fp64 C3: 248 GB fetched for 161 GB of reads).
+    // Measured at fp64 C3 (same box, profiles/r04_ab_dual64_*.json): 52.7 vs 59.3 ms per dual, 6.61 vs 6.44
+    // it/s.  PDHG_DUAL64=0 keeps the generic kernel.  The LDS-row and fused variants are fp32.
+    const bool dual64 = S == 8 && ny % 256 == 0 && tn.dual64.value_or(1) != 0;
+    int dual_one = 1;
+    if ((S == 4 || dual64) && ny % 256 == 0) {
+      pl.fast_dual = true;
+      // x rows through LDS (k_dual_lds_2d) for the fused-residual sweep; a context created for
+      // rho_alp_iters > 1 (no fused residual) sweeps row-per-thread: measured at C3 with rho_alp_iters = 10,
+      // k_dual_fast_2d 25.7 ms per sub-iteration against 38.1 for k_dual_lds_2d (2 waves per SIMD)
+      // fp64 (k_dual_lds_2d<EGNO, 8, false, double>, 230 VGPRs, no spill): the phi_bar x neighbours through LDS
+      // instead of the row-per-thread kernel's 1.25x re-reads from L2 (fp64 C3: 200 GB fetched for 161 GB of reads)
+      pl.dual_rx = (nx % 8 == 0 && !short_dual && !two_sets) ? 8 : 0;
+      if (tn.dual_rx) {   // 0 = row-per-thread kernel
+        const int v = *tn.dual_rx;
+        if (v == 0 || (((S == 4 && (v == 4 || v == 16)) || v == 8) && nx % v == 0)) pl.dual_rx = v;
+      }
+      if (S == 8 && pl.dual_rx == 8 && tn.dual_ypl.value_or(0) == 2) pl.dual_ypl = 2;
+      dual_one = tn.dual_one;
+      pl.NTd = pl.dual_rx ? pl.dual_rx * 64 : std::min(256, ny / 4);
+      pl.gxd = pl.dual_rx ? nx / pl.dual_rx : nx;
+      pl.gyd = pl.dual_rx ? ny / (64 * pl.dual_ypl) : (ny / 4 + pl.NTd - 1) / pl.NTd;
+      const int nJ0 = std::max(1, std::min(T, (2048 + pl.gxd * pl.gyd - 1) / (pl.gxd * pl.gyd)));
+      pl.jchunk_d = (T + nJ0 - 1) / nJ0;
+      pl.gzd = (T + pl.jchunk_d - 1) / pl.jchunk_d;
+    }
+    pl.dual_one = (pl.fast_dual && !pl.dual_rx && pl.jchunk_d == 1) ? dual_one : 0;
+    pl.rows_var = tn.rows_var;
+    pl.half_nt = tn.half_nt;
+    pl.res64_nt = tn.res64_nt;
+    pl.upd_pf = tn.upd_pf;
+    if (S == 4 && pl.ply.pow2 && ny >= 256 && ny <= 8192) {
+      pl.RWf = (ny == 8192) ? 4 : 8;
+      pl.NTf = std::min(1024, ny / 4);
+      if (pl.rows_var == 1 && (ny == 4096 || ny == 2048)) {   // 4 rows / block, 2 blocks per CU
+        pl.RWf = 4;
+        pl.NTf = ny / 8;
+      }
+      if (nx % pl.RWf == 0 && (pl.RWf * B) % 4 == 0) {
+        pl.fast_rows = true;
+        // residual task tiles of 8 time rows x 4 row groups (rows past the last whole tile run untiled)
+        pl.tile_j = ((nx / pl.RWf) % 4 == 0) ? 8 : 1;
+        if (tn.tile_j) {
+          const int v = *tn.tile_j;
+          if (v >= 1 && (v == 1 || (nx / pl.RWf) % 4 == 0)) pl.tile_j = v;
+        }
+        pl.lds_fast = (size_t)(pl.RWf / 2) * (ny + ny / 16) * csz;
+        // + the twiddle-seed table of the persistent kernels (fused residual, update; ny <= 4096)
+        pl.lds_fast_tw = pl.lds_fast + (ny <= 4096 ? (size_t)twlds_size(ny) * csz : 0);
+        pl.g_fast_upd = std::min((nx / pl.RWf) * T, 2048);
+      }
+    }
+    // fp64 residual: the fast row kernel on 4-row groups (2 complex lines of 4096 doubles = 136 KiB of LDS),
+    // rows read once per group over the sliding 3-row window, instead of the generic row-pair kernel's
+    // per-point neighbour re-reads (fp64 C3: 204 GB moved against 80.5 GB algorithmic)
+    if (S == 8 && pl.ply.pow2 && (ny == 2048 || ny == 4096) && nx % 4 == 0) {
+      pl.res64 = tn.res64.value_or(1) != 0;
+      if (pl.res64) {
+        pl.tile_j = ((nx / 4) % 4 == 0) ? 8 : 1;
+        pl.lds_res64 = (size_t)2 * (ny + ny / 16) * csz;
+        // the update through the fast row kernel too: + the twiddle-seed table (152 KiB at ny = 4096)
+        pl.lds_upd64 = pl.lds_res64 + (size_t)twlds_size(ny) * csz;
+        pl.g_fast_upd = std::min((nx / 4) * T, 2048);
+      }
+    }
+    // fp64 C3 shape: the residual spectrum handed to the x transform in task order (p.rspec; one contiguous run per
+    // 4-row task instead of 64-B chunks of the blocked layout), the x kernel's forward sweep reading it
+    // Interleaved A/B (round 5): C3's T = 200 118.8 -> 118.3 ms; its 25-row slab share (8 GPUs) 16.05 -> 16.35 ms
+    // (the x kernel's 64-B reads cost relatively more on short windows), so windows of >= 100 rows only
+    // (never on one-row windows: the T = 1 x kernel reads the blocked work buffer)
+    // (reads res64, f64_xt, half_real, B, t1_xt64)
+    const bool tc_ok = S == 8 && pl.res64 && ny == 4096 && pl.f64_xt && !pl.half_real && nxg == 4096 && B == 2 &&
+                       !xslab && T > 1 && !pl.t1_xt64;
+    pl.tc_spec = tc_ok && (tn.tc_spec ? *tn.tc_spec != 0 : T >= 100);
+    // fused residual: fp32 fast kernels with 8-row tiles on both sides, rho_alp_iters = 1 (in place),
+    // periodic bc, egno 1/2, single context; each dual workgroup must march the whole window (the
+    // residual row j needs rho'_{j+1}), so only grids with enough (x, y) tiles to fill the chip
+    // (PDHG_FUSE_RES=1 forces it for any eligible size, =0 turns it off)
+    // fp64: the sweep k_dual_lds_2d<.., double, YPL = 2> (128-column strips, 211 VGPRs) and the residual in
+    // half-tile tasks of 4 rows (k_res_fwdy_fused_2d<.., 4, 512, double>, the lines + twiddles fill the LDS)
+    // fp32 ny = 8192 (C4's y extent): the 4-row fast kernels, so the residual runs half-tile tasks as in fp64
+    // fp64 ny = 8192 (C4): the row pairs of the generic kernels (ip_rows) for the unfused residual and the update,
+    // the fused residual on quarter-tile tasks (one line of 8192 complex doubles)
+    // (reads fast_rows, RWf, res64, ip_rows, fast_dual, dual_rx, gxd, gyd; overwrites dual_ypl, gyd, jchunk_d, gzd)
+    const bool fr_rows = S == 4 ? (pl.fast_rows && (pl.RWf == 8 || (pl.RWf == 4 && ny == 8192)))
+                                : ((pl.res64 && (ny == 4096 || ny == 2048)) || (pl.ip_rows && ny == 8192));
+    if (pl.fast_dual && pl.dual_rx == 8 && fr_rows && pb.bc_x == 0 && pb.bc_y == 0 && pb.egno != 3 && !two_sets &&
+        !xslab) {
+      // fp32 ny = 8192 (4-row half-tile tasks, 16-B chunks of the B = 1 spectrum): round 4 measured it neutral
+      // (residual 31.2 -> 25.9 ms, dual 26.7 -> 31.3); with the XCD-ordered tasks (round 5, interleaved A/B at
+      // c4w50) the fused residual runs 22.9 ms against 30.3 unfused, step 88.25 -> 85.64 ms: on by default
+      pl.fuse_res = tn.fuse_res ? *tn.fuse_res != 0 : pl.gxd * pl.gyd >= 1024;
+      if (pl.fuse_res) {
+        if (S == 8) {
+          pl.dual_ypl = 2;
+          pl.gyd = ny / 128;
+        }
+        pl.jchunk_d = T;
+        pl.gzd = 1;
+      }
+    }
+    // C4 (ny = 8192 with half-real x blocks, B = 1): the fused residual's task-order spectrum + a transpose into the
+    // blocked layout instead of 16-B chunk stores (fp64 RW = 2 / fp32 RW = 4 tasks: 16-B elements)
+    pl.to_c4 = pl.fuse_res && pl.half_real && B == 1 && ny == 8192 && !xslab &&
+               (S == 8 ? pl.ip_rows : (pl.fast_rows && pl.RWf == 4)) && (nx % (S == 8 ? 64 : 128)) == 0 &&
+               tn.c4_to.value_or(1) != 0;
+    // threads of the fast row kernels as launched (ny = 4096: 512 instead of 1024 per half_nt); reads fuse_res
+    if (pl.fast_rows) {
+      pl.res_threads = (pl.NTf == 1024 && (pl.half_nt & 1) && pl.fuse_res) ? 512 : pl.NTf;
+      pl.upd_threads = (pl.NTf == 1024 && pl.RWf == 8 && (pl.half_nt & 2)) ? 512 : pl.NTf;
+    }
+  } else {
+    pl.lds_res = 2 * (size_t)nx * csz;
+    pl.gx1 = (T + 1) / 2;
+    pl.gx4 = std::min(pl.gx1, 2048);
+    if (pl.lds_res > kLdsBytes) {   // lines beyond LDS (C1: nx = 65536): Stockham passes over global scratch
+      pl.glb_line = true;
+      pl.lds_res = 0;
+      pl.nt1d = 1024;
+      // fp32 nx = 65536 (C1): four-step DHT over 16 + 9 workgroups of 1024 threads per row pair instead of
+      // one workgroup per pair (T = 400 gave 200 workgroups for 256 CUs): 1.41 -> 1.12 ms per iteration
+      // fp64 nx = 65536: the same 16 x 4096 split (kernels_fs16.hpp on complex doubles) instead of the
+      // generic Stockham passes over global scratch (fp64 C1: 3.9x the algorithmic bytes)
+      pl.fourstep = nx == 65536 && tn.fourstep.value_or(1) != 0;
+      pl.fs_wide = tn.fs_wide;
+      pl.fs16 = pl.fourstep && tn.fs16.value_or(1) != 0;
+      if (S == 8 && !pl.fs16) pl.fourstep = false;   // the other four-step forms are fp32
+      pl.f16_group = tn.f16_group;
+    }
+    pl.gx5 = (nx + 255) / 256;
+    pl.g5 = std::max(1, std::min(T, 8192 / std::max(1, pl.gx5)));
+    // chunked t-solve: one wave per 32-row chunk of 64 modes (T <= 512, Ct != 0)
+    pl.thomas_chunk = pb.Ct != 0.0 && T <= 16 * 32 && tn.thomas_chunk.value_or(1) != 0;
+    // fused 1-D residual (C1's 16 x 4096 path, rho_alp_iters = 1, periodic x): the dual sweep forms the residual
+    // rows (k_dual_1d_fr), stage A reads them (k_f16a_fwd_fused_1d); 8 time chunks of the sweep (reads fs16)
+    pl.fuse_res = pl.fs16 && pb.bc_x == 0 && !two_sets && pb.egno != 3 && nx % 256 == 0 &&
+                  tn.fuse_res1d.value_or(1) != 0;
+    pl.gz_1d = std::min(tn.fr1d_chunks, T);
+    pl.jchunk_1d = (T + pl.gz_1d - 1) / pl.gz_1d;
+    pl.gz_1d = (T + pl.jchunk_1d - 1) / pl.jchunk_1d;
+  }
+  pl.g_outer = tn.g_outer;
+  pl.head_xrun = tn.head_xrun;
+  // rho_alp_iters > 1 on the row-per-thread dual grid, single contexts: the dual loop in chunk passes of
+  // kMultiSub sub-iterations in registers (+ a final pass when the exit falls inside a chunk)
+  // Only where a pass is bandwidth-bound: C2's T = 1 marching windows (4 M points, the loop exiting after a few
+  // sub-iterations) ran 30.5 s with the chunks against 22.9 s per sub-iteration (launch-bound: the chunk computes
+  // 5 sub-iterations and the final pass re-runs k*), C2's T = 100 window 22.1 vs 10.5 it/s and C3 5.80 vs
+  // 3.00 it/s (round 4, fp64 / fp32, rho_alp_iters = 10)
+  const bool multi_ok = is2d && two_sets && pl.fast_dual && pl.dual_rx == 0 && !slab && !xslab &&
+                        pb.rho_alp_iters <= kDualMultiMax;
+  pl.dual_multi = multi_ok && (tn.dual_multi ? *tn.dual_multi != 0 : (double)T * nx * ny >= (double)(1 << 25));
+  // below that: the head form (sub-iteration 0 per-sub-iteration, the rest in chunks).  C2's marching windows exit
+  // after sub-iteration 0 in nearly every outer iteration, where 18 returning launches cost ~0.2 ms
+  pl.dual_head = multi_ok && !pl.dual_multi && tn.dual_head.value_or(1) != 0;
+  // the speculative schedule of iterate() needs the head form's one-sub-iteration shortcuts (k1_outer) and the
+  // two-launch fold / finalize (the halt flag is set by k_finalize_dual); reads dual_head, k1_outer, fold_fin
+  pl.spec_ok = pl.dual_head && pl.k1_outer && !pl.fold_fin && tn.spec.value_or(1) != 0;
+  pl.fin_merge = tn.fin_merge;
+  // (reads the dual grid after the fused residual's overwrite)
+  pl.partial_rows = std::max<size_t>(
+      {(size_t)pl.gx4 * pl.g4, (size_t)pl.gx5 * pl.g5, (size_t)pl.g_outer, (size_t)pl.g_fast_upd,
+       (size_t)pl.gxd * pl.gyd * (pl.gzd + 1), pl.fourstep ? (size_t)9 * ((T + 1) / 2) : 1, 1,
+       (pl.dual_multi || pl.dual_head) ? (size_t)kMultiSub * pl.gxd * pl.gyd * pl.gzd : (size_t)1});
+  if (xslab) {
+    // the row kernels that skip the ghost / padding rows: fp32 fast rows (ny in [256, 8192]), fp64 4-row kernels
+    if (!(is2d && (S == 4 ? pl.fast_rows : pl.res64) && pl.fast_dual && (pb.bc_x == 0 || pb.bc_x == 1) &&
+          pb.bc_y == 0))
+      return fail(PDHG_ERR_UNSUPPORTED, "x-slab decomposition needs ndim 2, bc (0,0) or (1,0) and a power-of-two ny "
+                                        "in [256, 8192] (fp32) or ny = 2048 / 4096 (fp64) (fast row and dual kernels)");
+    if (pl.nb % dc.P) return fail(PDHG_ERR_UNSUPPORTED, "%d column blocks do not split over %d ranks", pl.nb, dc.P);
+    pl.xs_nbs = pl.nb / dc.P;
+  }
+  // t-slab phases: the fast DHT x kernels (power-of-two nx 512 - 8192), the fp64 x kernel (nx = 4096, and 8192
+  // half-real) or the generic runtime-radix kernel (any nx, the DCT of egno 3's bc (1, 0)).  fp32 needs the
+  // fast row kernels; fp64 splits the residual's halo row off with the 4-row kernels (ny 2048 / 4096) and runs
+  // the generic row kernels over the whole slab after the halo otherwise
+  if (slab && !(is2d && (pl.fast_rows || S == 8)))
+    return fail(PDHG_ERR_UNSUPPORTED, "t-slab decomposition needs ndim 2 and, in fp32, a power-of-two ny in "
+                                      "[256, 8192] (fast row kernels)");
+  return PDHG_OK;
+}
+
+// the creation-time keys of pdhg_path_info / pdhg_plan_info (S = sizeof(real), ny / nx: the context's own)
+inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const std::string& k, int* value) {
+  if (k == "fused_residual") *value = pl.fuse_res ? 1 : 0;
+  else if (k == "fast_rows") *value = pl.fast_rows ? 1 : 0;
+  else if (k == "res64") *value = pl.res64 ? 1 : 0;
+  else if (k == "dual_multi") *value = pl.dual_multi ? 1 : 0;   // rho_alp_iters > 1: chunked dual passes
+  else if (k == "dual_head") *value = pl.dual_head ? 1 : 0;     // ... sub-iteration 0 alone, then the chunks
+  else if (k == "spec") *value = pl.spec_ok ? 1 : 0;   // iterate(): speculative one-sub-iteration schedule allowed
+  else if (k == "dual64") *value = (S == 8 && pl.fast_dual) ? 1 : 0;
+  else if (k == "fast_dual") *value = pl.fast_dual ? pl.dual_rx : -1;
+  else if (k == "dual_ypl") *value = pl.fast_dual && pl.dual_rx ? pl.dual_ypl : 0;
+  else if (k == "res64_nt") *value = pl.res64 ? (pb.ny == 2048 ? pl.res64_nt2048 : 512) : 0;
+  else if (k == "upd_t1") *value = (pl.res64 && pb.ny == 2048) ? pl.upd_t1 : 0;
+  else if (k == "t1_g16") *value = (pl.t1_g16 && (pb.nx == 2048 || pb.nx == 4096)) ? 1 : 0;
+  else if (k == "dual_one") *value = pl.dual_one ? 1 : 0;
+  else if (k == "fast_xt") *value = pl.fast_xt_code;
+  else if (k == "half_real") *value = pl.half_real ? 1 : 0;
+  else if (k == "fourstep") *value = pl.fourstep ? 1 : 0;
+  else if (k == "glb_line") *value = pl.glb_line ? 1 : 0;
+  else if (k == "ip_rows") *value = pl.ip_rows ? 1 : 0;   // fp64 ny = 8192 row pairs in one padded line
+  else if (k == "upd8192") *value = pl.upd8192 ? 1 : 0;   // fp64 ny = 8192: 2-row fast update
+  else if (k == "tc_spec") *value = pl.tc_spec ? 1 : 0;   // fp64 C3: task-order residual spectrum
+  else if (k == "to_c4") *value = pl.to_c4 ? 1 : 0;       // C4: task-order residual spectrum + transpose
+  else if (k == "thomas_chunk") *value = pl.thomas_chunk ? 1 : 0;
+  else if (k == "fs_wide") *value = (pl.fourstep && pl.fs_wide && !pl.fs16) ? 1 : 0;
+  else if (k == "fs16") *value = pl.fs16 ? 1 : 0;
+  else if (k == "rows_rw") *value = pl.fast_rows ? pl.RWf : 0;   // rows per fast row-kernel workgroup
+  else if (k == "row_threads") *value = pl.nt_row;
+  else if (k == "res_threads") *value = pl.res_threads;
+  else if (k == "upd_threads") *value = pl.upd_threads;
+  else if (k == "f64_xt") *value = pl.f64_xt ? 1 : 0;   // fp64 nx = 4096 x transform (kernels_xt_f64.hpp)
+  else if (k == "t1_xt64") *value = (pl.t1_xt64 && pl.t1_xt) ? 1 : 0;   // fp64 T = 1: carry-free x transform
+  else return false;
+  return true;
+}
+
+}  // namespace pdhg

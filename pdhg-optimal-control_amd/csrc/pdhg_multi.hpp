@@ -226,11 +226,12 @@ struct pdhg_multi {
     es = prob.precision == 8 ? 8 : 4;
     const int T = prob.T;
     if (P < 1 || P > T) return fail(PDHG_ERR_ARG, "need 1 <= ndev <= T (ndev %d, T %d)", P, T);
-    if (const char* e = getenv("PDHG_MULTI_PARTS")) parts = std::max(1, atoi(e));   // tuning override
-    if (const char* e = getenv("PDHG_MULTI_KCOPY")) kcopy = atoi(e) != 0;            // diagnostic
-    if (const char* e = getenv("PDHG_MULTI_SYNC")) sync_mask = (int)strtol(e, nullptr, 0);   // diagnostic
-    if (const char* e = getenv("PDHG_MULTI_ONESTREAM")) one_stream = atoi(e) != 0;          // diagnostic
-    if (const char* e = getenv("PDHG_MULTI_STEP_FENCE")) step_fence = atoi(e) != 0;
+    const pdhg::MultiTuning mt = pdhg::MultiTuning::from_env();
+    parts = mt.parts;
+    kcopy = mt.kcopy;
+    sync_mask = mt.sync_mask;
+    one_stream = mt.one_stream;
+    step_fence = mt.step_fence;
     const int base = T / P, extra = T % P;
     for (int q = 0, j = 0; q < P; ++q) {   // pdhg_amd.slab.slab_bounds
       const int n = base + (q < extra ? 1 : 0);
@@ -242,8 +243,7 @@ struct pdhg_multi {
     // (plain loads of another device's buffers, cross-device event order for the alternating contribution
     // buffers) is opt-in, PDHG_MULTI_PEER_FOLD=1, until a run on two real devices has shown it bitwise equal to
     // the gather fold; the default is the gather -> fold -> scatter chain on slab 0's device
-    peer_fold = false;
-    if (const char* e = getenv("PDHG_MULTI_PEER_FOLD")) peer_fold = P <= pdhg::kMultiMaxPeerFold && atoi(e) != 0;
+    peer_fold = P <= pdhg::kMultiMaxPeerFold && mt.peer_fold;
     for (int r = 0; r < P; ++r)
       for (int q = 0; q < P; ++q) {
         if (dev[r] == dev[q]) continue;
