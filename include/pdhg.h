@@ -55,7 +55,11 @@ typedef struct pdhg_problem {
   int bc_x, bc_y;    /* 0 periodic, 1 Neumann (egno 3: bc_x = 1)   run_example.py:229-240   */
   int nx, ny;        /* grid; ny = 1 when ndim == 1                                         */
   int T;             /* unknown time rows: phi is [T+1, nx(,ny)], rho / alp are [T, ...]    */
-  int precision;     /* 4 = fp32 (default, bench), 8 = fp64 (tight parity)                  */
+  int precision;     /* 4 = fp32 (throughput), 8 = fp64 (the reference's arithmetic; bench.py's
+                        default), 12 = mixed: fp32 state, tables and transforms with phi and
+                        phi_bar held, differenced and updated in fp64 (single 2-D contexts:
+                        pdhg_create; ndim 1, the slab and multi-device creates return
+                        PDHG_ERR_UNSUPPORTED).  Any other value: PDHG_ERR_ARG               */
   int rho_alp_iters; /* max dual sub-iterations per outer iteration (reference: 10)         */
   int reserved0;
   double dx, dy, dt;
@@ -102,6 +106,8 @@ int pdhg_destroy(pdhg_ctx* ctx);
  * get_state writes zeros there.  A null array is not transferred: set_state overwrites the given parts of the
  * current state and keeps the device's values of the others (window marching re-seeds phi alone when rho / alp
  * are the ones the device holds); it resets the iteration / stop bookkeeping either way. */
+/* A mixed context (precision 12) moves phi and phi_bar as full doubles in every call below (set_state followed by
+ * get_state returns phi bit for bit); rho and alp round to float as in an fp32 context. */
 int pdhg_set_state(pdhg_ctx* ctx, const double* phi, const double* rho, const double* alp);
 int pdhg_get_state(pdhg_ctx* ctx, double* phi, double* rho, double* alp);
 int pdhg_get_phi_bar(pdhg_ctx* ctx, double* phi_bar);   /* [T+1][nx][ny] */
@@ -170,7 +176,9 @@ int pdhg_device_bytes(pdhg_ctx* ctx, unsigned long long* bytes);
  * (fp64 C3 shape, windows of >= 100 rows: the residual spectrum in task order), "t1_xt64" 1/0 (fp64 one-row windows at a power-of-two nx in
  * 512..4096: the carry-free k_precond_x_t1_2d<..., double>; PDHG_T1_XT=0 off), "graph" 1/0 (pdhg_iterate replays
  * windows of iterations from a captured HIP graph; default on, environment PDHG_GRAPH=0 launches every
- * iteration eagerly), "graph_window" (iterations per replayed graph). */
+ * iteration eagerly), "graph_window" (iterations per replayed graph), "mixed" 1/0 (precision 12: fp32 state with
+ * fp64 phi / phi_bar; the other keys then answer for the fp32 kernels chosen -- "fast_dual" 0 and "fused_residual" 0
+ * always, the dual being the row-per-thread sweep or the generic per-point kernel -- and "dual64" is 0). */
 int pdhg_path_info(pdhg_ctx* ctx, const char* key, int* value);
 /* The same keys for the single context pdhg_create would build from `prob` under the current environment, without a
  * device: the problem is validated as in pdhg_create (same status codes) and the kernel paths are planned, nothing is
@@ -186,7 +194,8 @@ int pdhg_profile_enable(pdhg_ctx* ctx, int enable);
 int pdhg_profile_query(pdhg_ctx* ctx, const char* kernel_class, double* total_ms, int* launches);
 
 /* Algorithmic HBM bytes of one outer iteration for k dual
- * sub-iterations, and of one launch of the named kernel class. */
+ * sub-iterations, and of one launch of the named kernel class.  A mixed context prices phi / phi_bar at 8 bytes
+ * and everything else at 4 (update 28 N, dual 48 N against 16 N / 44 N in fp32 and 32 N / 88 N in fp64). */
 int pdhg_algorithmic_bytes(pdhg_ctx* ctx, int k, const char* kernel_class, double* bytes);
 
 /* ---------------- t-slab decomposition (multi-GPU) ----------------

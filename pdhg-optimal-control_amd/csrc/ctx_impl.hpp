@@ -58,13 +58,26 @@ struct ImplBase {
 template <int V>
 using IC = std::integral_constant<int, V>;
 
-template <typename R>
+// R: the arithmetic of the state, the tables and the transforms; P: the type phi and phi_bar are held in (P = double
+// with R = float is the mixed context, precision 12: kp.phi / kp.phibar stay null, px carries the double pair)
+template <typename R, typename P = R>
 struct Impl : ImplBase {
   using C = cplx<R>;
   using Real = R;
+  static constexpr bool kMixed = !std::is_same<R, P>::value;
+  static_assert(!kMixed || (sizeof(R) == 4 && sizeof(P) == 8), "mixed: float state, double phi / phi_bar");
   pdhg_problem pb{};
   hipStream_t stream = nullptr;
   KP<R> kp{};
+  PhiX<R, P> px{};
+  P* phi_dev() const {
+    if constexpr (kMixed) return px.phi;
+    else return kp.phi;
+  }
+  P* phibar_dev() const {
+    if constexpr (kMixed) return px.phibar;
+    else return kp.phibar;
+  }
   C* twx = nullptr;
   C* twy = nullptr;
   std::vector<void*> allocs;
@@ -167,7 +180,7 @@ struct Impl : ImplBase {
     HIP_TRY(hipHostMalloc((void**)&h_done, sizeof(int), hipHostMallocDefault));
     const bool is2d = pb.ndim == 2;
     std::string why;
-    const Decomp dc{slab, slab_j0, slab_Tg, xslab, xs_rank, xs_P, xs_nxg, xs_nloc};
+    const Decomp dc{slab, slab_j0, slab_Tg, xslab, xs_rank, xs_P, xs_nxg, xs_nloc, kMixed};
     if (int rc = plan_paths(pb, (int)sizeof(R), dc, tun, pp, why)) return fail(rc, "%s", why.c_str());
     const int na = pp.na;
     const bool two_sets = pp.two_sets, fs16 = pp.fs16;
@@ -215,8 +228,20 @@ struct Impl : ImplBase {
     // ---- device buffers ----
     const size_t npl = plane();
     int rc;
-    if ((rc = alloc(&p.phi, (size_t)(T + 1) * npl))) return rc;
-    if ((rc = alloc(&p.phibar, (size_t)(T + 1) * npl))) return rc;
+    if constexpr (kMixed) {
+      p.phi = p.phibar = nullptr;
+      if ((rc = alloc(&px.phi, (size_t)(T + 1) * npl))) return rc;
+      if ((rc = alloc(&px.phibar, (size_t)(T + 1) * npl))) return rc;
+      px.inv_dx = 1.0 / pb.dx;
+      px.inv_dy = 1.0 / pb.dy;
+      px.inv_dt = 1.0 / pb.dt;
+      px.inv_dx2 = 1.0 / (pb.dx * pb.dx);
+      px.inv_dy2 = 1.0 / (pb.dy * pb.dy);
+      px.epsl = pb.epsl;
+    } else {
+      if ((rc = alloc(&p.phi, (size_t)(T + 1) * npl))) return rc;
+      if ((rc = alloc(&p.phibar, (size_t)(T + 1) * npl))) return rc;
+    }
     const size_t nwork = is2d ? (size_t)T * p.nb * nx * p.B : (size_t)T * nx;
     if ((rc = alloc(&p.work, nwork))) return rc;
     for (int s = 0; s < (two_sets ? 2 : 1); ++s) {
@@ -580,11 +605,11 @@ struct Impl : ImplBase {
   int launch_thomas_1d(const KP<R>& p) {
     if (!pp.thomas_chunk) return launch(k_thomas_1d<R>, dim3((pb.nx + 255) / 256), dim3(256), 0, p);
     if constexpr (sizeof(R) == 4) {   // one 32-row chunk per wave
-      const int P = (pb.T + 31) / 32;
-      return launch(k_thomas_chunk_1d<32, 1, R>, dim3((pb.nx + 63) / 64), dim3(64 * P), 0, p);
+      const int NP = (pb.T + 31) / 32;
+      return launch(k_thomas_chunk_1d<32, 1, R>, dim3((pb.nx + 63) / 64), dim3(64 * NP), 0, p);
     } else {                           // one 16-row chunk per half-wave (32 modes per workgroup)
-      const int P = (pb.T + 15) / 16;
-      return launch(k_thomas_chunk_1d<16, 2, R>, dim3((pb.nx + 31) / 32), dim3(64 * ((P + 1) / 2)), 0, p);
+      const int NP = (pb.T + 15) / 16;
+      return launch(k_thomas_chunk_1d<16, 2, R>, dim3((pb.nx + 31) / 32), dim3(64 * ((NP + 1) / 2)), 0, p);
     }
   }
 
@@ -711,6 +736,25 @@ struct Impl : ImplBase {
         return launch(k_invy_update_fast_2d<8192, 2, 512, 2, double>, gf, dim3(512),
                       (size_t)Pad<8192>::LINE * sizeof(C), p, twy);
     }
+    if constexpr (kMixed) {   // the fp32 shapes with double phi rows; one prefetch depth (kMixedUpdPF) at 512 threads
+      if (pp.fast_rows)
+        return with_fast_rows([&](auto Nc, auto RWc, auto NTc) {
+          constexpr int N_ = decltype(Nc)::value, RW_ = decltype(RWc)::value, NT_ = decltype(NTc)::value;
+          if constexpr (NT_ == 1024 && RW_ == 8) {
+            if (pp.upd_threads == 512)
+              return launch(k_invy_update_fast_mixed_2d<N_, RW_, 512, kMixedUpdPF>, gf, dim3(512), pp.lds_fast_tw, p,
+                            twy, px);
+          }
+          return launch(k_invy_update_fast_mixed_2d<N_, RW_, NT_>, gf, dim3(NT_), pp.lds_fast_tw, p, twy, px);
+        });
+      upd_rows = pp.gx4 * pp.g4;
+      return with_line_fft(pp.ply, [&](auto f) {
+        using F = decltype(f);
+        if (pp.nt_row <= 256)
+          return launch(k_invy_update_mixed_2d<F, 256>, dim3(pp.gx4), dim3(pp.nt_row), pp.lds_res, p, f, twy, px);
+        return launch(k_invy_update_mixed_2d<F, 1024>, dim3(pp.gx4), dim3(pp.nt_row), pp.lds_res, p, f, twy, px);
+      });
+    }
     if (pp.fast_rows)
       return with_fast_rows([&](auto Nc, auto RWc, auto NTc) {
         constexpr int N_ = decltype(Nc)::value, RW_ = decltype(RWc)::value, NT_ = decltype(NTc)::value;
@@ -764,6 +808,7 @@ struct Impl : ImplBase {
       }
       return launch(k_finalize_primal, dim3(1), dim3(1024), 0, p.partials, upd_rows, 1, p.ctrl);
     }
+    if constexpr (kMixed) return fail(PDHG_ERR_STATE, "mixed context is 2-D only");
     if (pp.fourstep) return launch_fourstep_1d(p);
     {
       ProfScope ps(this, "residual");
@@ -873,6 +918,13 @@ struct Impl : ImplBase {
     return with_egno<3>([&](auto eg) {
       constexpr int E = decltype(eg)::value;
       auto sweep = [&](auto kern) { return launch(kern, g, dim3(pp.NTd), 0, p, pp.jchunk_d, lo, hi, zbase); };
+      if constexpr (kMixed) {   // row-per-thread only (plan_paths: dual_rx = 0, no fused residual)
+        if (pp.dual_rx || pp.fuse_res) return fail(PDHG_ERR_STATE, "mixed context planned an LDS-row dual");
+        res_valid = false;
+        if (pp.dual_one)
+          return launch(k_dual_fast_mixed_2d<E, 1>, g, dim3(pp.NTd), 0, p, pp.jchunk_d, lo, hi, zbase, px);
+        return launch(k_dual_fast_mixed_2d<E>, g, dim3(pp.NTd), 0, p, pp.jchunk_d, lo, hi, zbase, px);
+      }
       if constexpr (E != 3) {
         if (pp.fuse_res && p.inplace && g.z == 1 && (slab || (lo == 0 && hi == pb.T))) {
           int rc;
@@ -911,14 +963,21 @@ struct Impl : ImplBase {
     return with_egno<3>([&](auto eg) {
       constexpr int E = decltype(eg)::value;
       int rc;
+      // one chunk (FINAL false) or final pass of the context's phi type
+      auto pass = [&](auto fin, int slo) {
+        constexpr bool FIN = decltype(fin)::value != 0;
+        if constexpr (kMixed)
+          return launch(k_dual_multi_mixed_2d<E, NS, FIN>, g, b, 0, p, slo, k, rows, pp.jchunk_d, 0, pb.T, 0, xrun, px);
+        else
+          return launch(k_dual_multi_2d<E, R, NS, FIN>, g, b, 0, p, slo, k, rows, pp.jchunk_d, 0, pb.T, 0, xrun);
+      };
       for (int slo = slo0; slo < k; slo += NS) {
-        if ((rc = launch(k_dual_multi_2d<E, R, NS, false>, g, b, 0, p, slo, k, rows, pp.jchunk_d, 0, pb.T, 0, xrun)))
-          return rc;
+        if ((rc = pass(IC<0>{}, slo))) return rc;
         if ((rc = launch(k_finalize_dual_multi, dim3(1), dim3(1024), 0, p.partials, rows, std::min(NS, k - slo), slo, k,
                          pp.na, pp.n_dead, eps, p.ctrl)))
           return rc;
       }
-      return launch(k_dual_multi_2d<E, R, NS, true>, g, b, 0, p, 0, k, rows, pp.jchunk_d, 0, pb.T, 0, xrun);
+      return pass(IC<1>{}, 0);
     });
   }
 
@@ -930,6 +989,10 @@ struct Impl : ImplBase {
     if (pb.ndim == 2 && pp.fast_dual) {
       nrows = pp.gxd * pp.gyd * pp.gzd;
       return launch_dual_fast(p);
+    }
+    if constexpr (kMixed) {
+      if (pb.ndim != 2) return fail(PDHG_ERR_STATE, "mixed context is 2-D only");
+      return with_egno<3>([&](auto eg) { return launch(k_dual_mixed_2d<decltype(eg)::value>, g, dim3(256), 0, p, px); });
     }
     if (pb.ndim == 2)
       return with_egno<3>([&](auto eg) { return launch(k_dual_2d<R, decltype(eg)::value>, g, dim3(256), 0, p); });
@@ -1488,7 +1551,8 @@ struct Impl : ImplBase {
   int n_ctrl() const { return (pb.ndim == 1 || pb.egno == 3) ? 1 : 2; }
   int n_alp_ref() const { return pb.ndim == 1 ? 2 : 4; }
 
-  void compute_row0_sq(const std::vector<R>& row0) {
+  template <typename E>
+  void compute_row0_sq(const std::vector<E>& row0) {
     double s = 0.0;   // live rows only (x-slab: [xl0, xl1) of the padded local rows)
     const size_t ny = pb.ny;
     for (size_t i = (size_t)kp.xl0 * ny; i < (size_t)kp.xl1 * ny; ++i) s += (double)row0[i] * (double)row0[i];
@@ -1517,10 +1581,16 @@ struct Impl : ImplBase {
       }
     };
     if (phi) {
-      const R* src = src_of(phi, nphi);
-      H2D(kp.phi, src, nphi * sizeof(R));
-      H2D(kp.phibar, src, nphi * sizeof(R));
-      compute_row0_sq(std::vector<R>(src, src + npl));
+      if constexpr (kMixed) {   // phi as given: full doubles
+        H2D(px.phi, phi, nphi * sizeof(P));
+        H2D(px.phibar, phi, nphi * sizeof(P));
+        compute_row0_sq(std::vector<P>(phi, phi + npl));
+      } else {
+        const R* src = src_of(phi, nphi);
+        H2D(kp.phi, src, nphi * sizeof(R));
+        H2D(kp.phibar, src, nphi * sizeof(R));
+        compute_row0_sq(std::vector<R>(src, src + npl));
+      }
     }
     const size_t n = (size_t)T * npl;
     if (rho) H2D(kp.rho[cur], src_of(rho, n), n * sizeof(R));
@@ -1551,6 +1621,10 @@ struct Impl : ImplBase {
 
   int set_phi_bar(const double* pbar) {
     const size_t n = (size_t)(pb.T + 1) * plane();
+    if constexpr (sizeof(P) == 8) {
+      H2D(phibar_dev(), pbar, n * sizeof(P));
+      return PDHG_OK;
+    }
     std::vector<R> buf(n);
     for (size_t i = 0; i < n; ++i) buf[i] = (R)pbar[i];
     H2D(kp.phibar, buf.data(), n * sizeof(R));
@@ -1560,6 +1634,10 @@ struct Impl : ImplBase {
   int get_phi_bar(double* pbar) {
     HIP_TRY(hipStreamSynchronize(stream));
     const size_t n = (size_t)(pb.T + 1) * plane();
+    if constexpr (kMixed) {
+      HIP_TRY(hipMemcpy(pbar, px.phibar, n * sizeof(P), hipMemcpyDeviceToHost));
+      return PDHG_OK;
+    }
     std::vector<R> buf(n);
     HIP_TRY(hipMemcpy(buf.data(), kp.phibar, n * sizeof(R), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) pbar[i] = (double)buf[i];
@@ -1578,17 +1656,18 @@ struct Impl : ImplBase {
     std::unique_ptr<R[]> buf(new R[nphi]);   // not value-initialised: every element read is copied in first
     const size_t n = (size_t)T * npl;
     // fp64 planes straight into the caller's arrays (same layout); fp32 through the buffer and a widening copy
-    auto plane_out = [&](double* dst, const R* src, size_t cnt) -> int {
-      if constexpr (sizeof(R) == 8) {
-        HIP_TRY(hipMemcpy(dst, src, cnt * sizeof(R), hipMemcpyDeviceToHost));
+    auto plane_out = [&](double* dst, const auto* src, size_t cnt) -> int {
+      using E = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+      if constexpr (sizeof(E) == 8) {
+        HIP_TRY(hipMemcpy(dst, src, cnt * sizeof(E), hipMemcpyDeviceToHost));
       } else {
-        HIP_TRY(hipMemcpy(buf.get(), src, cnt * sizeof(R), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(buf.get(), src, cnt * sizeof(E), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < cnt; ++i) dst[i] = (double)buf[i];
       }
       return PDHG_OK;
     };
-    if (phi && (rc = plane_out(phi, kp.phi, nphi))) return rc;
-    if (rho && (rc = plane_out(rho, kp.rho[cur], n))) return rc;
+    if (phi && (rc = plane_out(phi, (const P*)phi_dev(), nphi))) return rc;
+    if (rho && (rc = plane_out(rho, (const R*)kp.rho[cur], n))) return rc;
     if (alp) {
       const int nc = n_ctrl(), nar = n_alp_ref();
       std::memset(alp, 0, sizeof(double) * n * nc * nar);
@@ -1613,18 +1692,19 @@ struct Impl : ImplBase {
     if ((rc = read_ctrl(h))) return rc;
     const size_t npl = plane(), n = (size_t)nrows * npl, off = (size_t)row0 * npl;
     std::unique_ptr<R[]> buf(sizeof(R) == 8 && !alp ? nullptr : new R[n]);
-    auto rows_out = [&](double* dst, const R* src) -> int {
-      if constexpr (sizeof(R) == 8) {
-        HIP_TRY(hipMemcpy(dst, src + off, n * sizeof(R), hipMemcpyDeviceToHost));
+    auto rows_out = [&](double* dst, const auto* src) -> int {
+      using E = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
+      if constexpr (sizeof(E) == 8) {
+        HIP_TRY(hipMemcpy(dst, src + off, n * sizeof(E), hipMemcpyDeviceToHost));
       } else {
-        HIP_TRY(hipMemcpy(buf.get(), src + off, n * sizeof(R), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(buf.get(), src + off, n * sizeof(E), hipMemcpyDeviceToHost));
         for (size_t i = 0; i < n; ++i) dst[i] = (double)buf[i];
       }
       return PDHG_OK;
     };
-    if (phi && (rc = rows_out(phi, kp.phi))) return rc;
-    if (pbar && (rc = rows_out(pbar, kp.phibar))) return rc;
-    if (rho && (rc = rows_out(rho, kp.rho[h.cur]))) return rc;
+    if (phi && (rc = rows_out(phi, (const P*)phi_dev()))) return rc;
+    if (pbar && (rc = rows_out(pbar, (const P*)phibar_dev()))) return rc;
+    if (rho && (rc = rows_out(rho, (const R*)kp.rho[h.cur]))) return rc;
     if (alp) {
       const int nc = n_ctrl(), nar = n_alp_ref();
       std::memset(alp, 0, sizeof(double) * n * nc * nar);
@@ -1642,15 +1722,15 @@ struct Impl : ImplBase {
     res_valid = false;
     const size_t npl = plane();
     const int T = pb.T;
-    std::vector<R> row(npl);
-    for (size_t i = 0; i < npl; ++i) row[i] = (R)g[i];
+    std::vector<P> row(npl);   // phi's type (mixed: g as given)
+    for (size_t i = 0; i < npl; ++i) row[i] = (P)g[i];
     compute_row0_sq(row);
-    R* d_row;
-    HIP_TRY(hipMalloc((void**)&d_row, npl * sizeof(R)));
-    H2D(d_row, row.data(), npl * sizeof(R));
+    P* d_row;
+    HIP_TRY(hipMalloc((void**)&d_row, npl * sizeof(P)));
+    H2D(d_row, row.data(), npl * sizeof(P));
     const int grid = 4096;
-    hipLaunchKernelGGL((k_bcast_rows<R>), dim3(grid), dim3(256), 0, stream, kp.phi, d_row, npl, T + 1);
-    hipLaunchKernelGGL((k_bcast_rows<R>), dim3(grid), dim3(256), 0, stream, kp.phibar, d_row, npl, T + 1);
+    hipLaunchKernelGGL((k_bcast_rows<P>), dim3(grid), dim3(256), 0, stream, phi_dev(), d_row, npl, T + 1);
+    hipLaunchKernelGGL((k_bcast_rows<P>), dim3(grid), dim3(256), 0, stream, phibar_dev(), d_row, npl, T + 1);
     hipLaunchKernelGGL((k_fill<R>), dim3(grid), dim3(256), 0, stream, kp.rho[0], (size_t)T * npl, (R)pb.c_on_rho);
     for (int a = 0; a < pp.na; ++a)
       hipLaunchKernelGGL((k_fill<R>), dim3(grid), dim3(256), 0, stream, kp.alp[0][a], (size_t)T * npl, (R)0);
@@ -1707,20 +1787,22 @@ struct Impl : ImplBase {
   double algorithmic_bytes(int k, const std::string& cls) const {
     const double N = (double)pb.T * (double)(kp.xl1 - kp.xl0) * (double)pb.ny;   // live rows (x-slab)
     const double S = (double)sizeof(R);
+    const double X = (double)sizeof(P) - S;   // mixed: the extra bytes of a phi / phi_bar element (else 0)
     const bool d2 = pb.ndim == 2;
     const double nr = 1.0 + pp.na;   // rho + live alp arrays
     if (cls == "iteration") {
       // 2-D 4N(14 + 11k + 5[k>1]), 1-D 4N(12 + 7k + 3[k>1]); generalised to S and na
-      if (d2) return S * N * (14.0 + 11.0 * k + 5.0 * (k > 1));
+      // (of those, phi / phi_bar: 3 in the update and 1 per dual sub-iteration)
+      if (d2) return S * N * (14.0 + 11.0 * k + 5.0 * (k > 1)) + X * N * (3.0 + k);
       return S * N * (12.0 + 7.0 * k + 3.0 * (k > 1));
     }
     // fused residual: the dual also writes the residual rows (+1), the tile-edge row terms (2 rows per 8)
     // and the strip-edge column terms (2 per 256); the residual kernel reads them and writes the spectrum
     const double edge = !pp.fuse_res ? 0.0 : d2 ? 2.0 / 8.0 + 2.0 / (64.0 * pp.dual_ypl) : 2.0 / 64.0;   // 1-D: per wave
-    if (cls == "dual") return S * N * (1.0 + 2.0 * nr + (pp.fuse_res ? 1.0 + edge : 0.0));
+    if (cls == "dual") return S * N * (1.0 + 2.0 * nr + (pp.fuse_res ? 1.0 + edge : 0.0)) + X * N;
     if (cls == "residual") return S * N * (pp.fuse_res ? 2.0 + edge : nr + 1.0);
     if (cls == "precond") return S * N * (d2 ? 4.0 : 2.0);   // 2-D: x-DHT+Thomas fwd (2N) + bwd+x-DHT (2N)
-    if (cls == "update") return S * N * 4.0;                 // read U, phi; write phi, phi_bar
+    if (cls == "update") return S * N * 4.0 + X * N * 3.0;   // read U, phi; write phi, phi_bar
     return -1.0;
   }
 };

@@ -10,6 +10,7 @@
 // column block is one contiguous [nx][B] slab (= B/2 interleaved complex lines
 // for the x transform) and a row's block segment is B contiguous values.
 #pragma once
+#include <type_traits>
 #include "params.hpp"
 
 namespace pdhg {
@@ -327,6 +328,58 @@ __global__ void __launch_bounds__(512) k_precond_xt_2d(KP<R> p, F plx, const cpl
 // G workgroups striding over the (T x npairs) row-pair tasks (XCD-aware, as k_res_fwdy_2d);
 // block nt_row (as k_res_fwdy_2d); LDS 2 * ny complex.
 // sums: [0] sum (phi'-phi)^2, [1] sum phi^2 (old), [2] sum phi'^2 (NaN detector)
+// invy_update_2d_body<.., P>: k_invy_update_2d (below) with phi / phi_bar in P, for the mixed context's
+// k_invy_update_mixed_2d: U in float out of the transform, phi' = phi + (double)(tau / n) (double)U, phi_bar and the
+// sums in double.  The fp32 / fp64 kernel keeps its own text: routed through this body its code came out differently
+// scheduled and contracted (states off in the last bit), and those results must not move.
+template <typename R, class F, typename P = R>
+__device__ __forceinline__ void invy_update_2d_body(const KP<R>& p, const PhiX<R, P>& px, F ply,
+                                                    const cplx<R>* __restrict__ twy) {
+  using C = cplx<R>;
+  if (p.ctrl->done) return;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  C* A = reinterpret_cast<C*>(smem_raw);
+  C* Bf = A + ply.n();
+  const int nx = p.nx, ny = p.ny, B = p.B, nb = p.nb;
+  const int npairs = (nx + 1) >> 1;
+  const int ntask = npairs * p.T;
+  const size_t plane = (size_t)nx * ny;
+  const R scale = p.tau * p.inv_n;
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int task = xcd_remap(blockIdx.x, gridDim.x); task < ntask; task += gridDim.x) {
+    const int j = task / npairs;
+    const int x0 = 2 * (task - j * npairs);
+    const R* wk = p.work + (size_t)j * nb * nx * B;
+    P* phi = phi_of(p, px) + (size_t)(j + 1) * plane;
+    P* pbar = phibar_of(p, px) + (size_t)(j + 1) * plane;
+    const bool has2 = (x0 + 1) < nx;
+    for (int ky = threadIdx.x; ky < ny; ky += blockDim.x) {
+      const int b = ky >> p.lB, c = ky & (B - 1);
+      const R* srcp = wk + ((size_t)b * nx + x0) * B + c;
+      A[fpos<F>(ky)] = cmk<C>(srcp[0], has2 ? srcp[B] : (R)0);
+    }
+    __syncthreads();
+    const C* Z = ply.template run<C>(A, Bf, twy);
+    for (int y = threadIdx.x; y < ny; y += blockDim.x) {
+      R u0, u1;
+      hartley_line<F, C, R>(Z, ny, y, u0, u1);
+      for (int r = 0; r < 2; ++r) {
+        if (r == 1 && !has2) break;
+        const size_t idx = (size_t)(x0 + r) * ny + y;
+        const P old = phi[idx];
+        const P nw = old + (P)scale * (P)(r ? u1 : u0);
+        phi[idx] = nw;
+        pbar[idx] = (P)2 * nw - old;
+        const double d = (double)nw - (double)old;
+        s[0] += d * d;
+        s[1] += (double)old * (double)old;
+        s[2] += (double)nw * (double)nw;
+      }
+    }
+    __syncthreads();
+  }
+  block_reduce_store<3>(s, p.partials, blockIdx.x);
+}
 template <typename R, class F, int NTB>
 __global__ void __launch_bounds__(NTB) k_invy_update_2d(KP<R> p, F ply, const cplx<R>* __restrict__ twy) {
   using C = cplx<R>;
@@ -374,6 +427,11 @@ __global__ void __launch_bounds__(NTB) k_invy_update_2d(KP<R> p, F ply, const cp
   }
   block_reduce_store<3>(s, p.partials, blockIdx.x);
 }
+template <class F, int NTB>
+__global__ void __launch_bounds__(NTB) k_invy_update_mixed_2d(KP<float> p, F ply, const float2* __restrict__ twy,
+                                                              PhiX<float, double> px) {
+  invy_update_2d_body<float, F, double>(p, px, ply, twy);
+}
 
 // One grid point of the dual step (update_fns_in_pdhg.py:150-165): alpha prox from the one-sided
 // differences of phi_bar at row j+1, HJ residual (:58-70), rho prox (update_rho_2d, :115-119).
@@ -388,6 +446,22 @@ struct DualPre {
 };
 template <typename R>
 __device__ __forceinline__ DualPre<R> dual_pre(const KP<R>& p, R pc, R pxm, R pxp, R pym, R pyp, R f0c) {
+  DualPre<R> d;
+  d.DxR = (pxp - pc) * p.inv_dx;
+  d.DxL = (pc - pxm) * p.inv_dx;
+  d.DyR = (pyp - pc) * p.inv_dy;
+  d.DyL = (pc - pym) * p.inv_dy;
+  R vec = (pc - f0c) * p.inv_dt;
+  if (p.epsl != (R)0) {
+    vec = vec - p.epsl * ((pxp + pxm - (R)2 * pc) * p.inv_dx2);
+    vec = vec - p.epsl * ((pyp + pym - (R)2 * pc) * p.inv_dy2);
+  }
+  d.vec0 = vec;
+  return d;
+}
+// the same on a mixed context's double reciprocals (PhiX), R = double
+template <typename R>
+__device__ __forceinline__ DualPre<R> dual_pre(const PhiX<float, R>& p, R pc, R pxm, R pxp, R pym, R pyp, R f0c) {
   DualPre<R> d;
   d.DxR = (pxp - pc) * p.inv_dx;
   d.DxL = (pc - pxm) * p.inv_dx;
@@ -477,9 +551,77 @@ __device__ __forceinline__ R dual_point(const KP<R>& p, R pc, R pxm, R pxp, R py
   return nmax<R>(rho + p.sigma * vec, (R)0);
 }
 
+// A mixed context's point (phi_bar and its neighbours double, the state float): the four one-sided differences and the
+// time / eps terms in double (dual_pre<double> on the PhiX reciprocals), rounded to float once, then dual_core<float>.
+// (P == R: dual_point)
+template <typename R, int EGNO, typename P>
+__device__ __forceinline__ R dual_point_x(const KP<R>& p, const PhiX<R, P>& px, P pc, P pxm, P pxp, P pym, P pyp, P f0c,
+                                          R rho, const R* ao, R axc, R ayc, R* an) {
+  if constexpr (std::is_same<R, P>::value) {
+    return dual_point<R, EGNO>(p, pc, pxm, pxp, pym, pyp, f0c, rho, ao, axc, ayc, an);
+  } else {
+    const DualPre<P> dd = dual_pre<P>(px, pc, pxm, pxp, pym, pyp, f0c);
+    const DualPre<R> d{(R)dd.DxR, (R)dd.DxL, (R)dd.DyR, (R)dd.DyL, (R)dd.vec0};
+    return dual_core<R, EGNO>(p, d, rho, ao, axc, ayc, an);
+  }
+}
+
 // grid: (ceil(ny/256), G) where the G workgroup rows stride over the T*nx (j, x) rows; block 256
 // sums: [0] sum (rho'-rho)^2 [1] sum rho'^2 [2] sum rho^2, then per live alpha array a:
 //       [3+3a] sum (alp'-alp)^2 [4+3a] sum alp'^2 [5+3a] sum alp^2
+// dual_2d_body<.., P>: k_dual_2d (below) with phi_bar in P, for the mixed context's k_dual_mixed_2d (float state,
+// double phi_bar); the fp32 / fp64 kernel keeps its own text (see invy_update_2d_body)
+template <typename R, int EGNO, typename P = R>
+__device__ __forceinline__ void dual_2d_body(const KP<R>& p, const PhiX<R, P>& px) {
+  if (p.ctrl->done || p.ctrl->inner_done) return;
+  const int cur = p.ctrl->cur;
+  const int src_set = (p.inplace || p.sub == 0) ? cur : 1 - cur;
+  const int dst_set = p.inplace ? cur : 1 - cur;
+  const int nx = p.nx, ny = p.ny;
+  const int y = blockIdx.x * blockDim.x + threadIdx.x;
+  constexpr int NA = (EGNO == 3) ? 2 : 4;
+  constexpr int NS = 3 + 3 * NA;
+  double s[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[i] = 0.0;
+  const size_t plane = (size_t)nx * ny;
+  const int nrows = p.T * nx;
+  const int ym = nb_index(y - 1, ny, p.bcy), yp = nb_index(y + 1, ny, p.bcy);
+  const R ayc = (y < ny) ? p.ay[y] : (R)0;
+  for (int row = blockIdx.y; row < nrows && y < ny; row += gridDim.y) {
+    const int j = row / nx;
+    const int x = row - j * nx;
+    const size_t c = (size_t)x * ny + y;
+    const P* f1 = phibar_of(p, px) + (size_t)(j + 1) * plane;   // phi_bar row j+1
+    const P* f0 = phibar_of(p, px) + (size_t)j * plane;         // phi_bar row j
+    const int xm = nb_index(x - 1, nx, p.bcx), xp = nb_index(x + 1, nx, p.bcx);
+    const P pc = f1[c];
+    const P pxm = (xm >= 0) ? f1[(size_t)xm * ny + y] : (P)0;
+    const P pxp = (xp >= 0) ? f1[(size_t)xp * ny + y] : (P)0;
+    const P pym = (ym >= 0) ? f1[(size_t)x * ny + ym] : (P)0;
+    const P pyp = (yp >= 0) ? f1[(size_t)x * ny + yp] : (P)0;
+    const size_t o = (size_t)j * plane + c;
+    const R rho = p.rho[src_set][o];
+    R an[4], ao[4];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) ao[a] = p.alp[src_set][a][o];
+    const R rn = dual_point_x<R, EGNO, P>(p, px, pc, pxm, pxp, pym, pyp, f0[c], rho, ao, p.ax[x], ayc, an);
+    p.rho[dst_set][o] = rn;
+    const double dr = (double)rn - (double)rho;
+    s[0] += dr * dr;
+    s[1] += (double)rn * (double)rn;
+    s[2] += (double)rho * (double)rho;
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      p.alp[dst_set][a][o] = an[a];
+      const double da = (double)an[a] - (double)ao[a];
+      s[3 + 3 * a] += da * da;
+      s[4 + 3 * a] += (double)an[a] * (double)an[a];
+      s[5 + 3 * a] += (double)ao[a] * (double)ao[a];
+    }
+  }
+  block_reduce_store<NS>(s, p.partials, blockIdx.y * gridDim.x + blockIdx.x);
+}
 template <typename R, int EGNO>
 __global__ void __launch_bounds__(256) k_dual_2d(KP<R> p) {
   if (p.ctrl->done || p.ctrl->inner_done) return;
@@ -530,6 +672,10 @@ __global__ void __launch_bounds__(256) k_dual_2d(KP<R> p) {
     }
   }
   block_reduce_store<NS>(s, p.partials, blockIdx.y * gridDim.x + blockIdx.x);
+}
+template <int EGNO>
+__global__ void __launch_bounds__(256) k_dual_mixed_2d(KP<float> p, PhiX<float, double> px) {
+  dual_2d_body<float, EGNO, double>(p, px);
 }
 
 }  // namespace pdhg

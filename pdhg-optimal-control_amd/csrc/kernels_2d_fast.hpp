@@ -561,6 +561,153 @@ __global__ void __launch_bounds__(256) k_res_fwdy_fused_transpose_2d(KP<R> p, in
 // RW = 2 with B = 1 (fp64 at C4's ny = 8192 with the half-real x blocks): one line, 16-B chunks.
 // G16: only the first twiddled pass's seeds in LDS, the later passes' from twy (bitwise the same transform; fp64 ny = 2048
 // with 256 threads: 70.4 KiB of LDS, two workgroups per CU -- the one-row windows' update)
+// invy_update_fast_body<.., P>: k_invy_update_fast_2d (below) with phi / phi_bar in P, for the mixed context's
+// k_invy_update_fast_mixed_2d: the spectrum, the transform and U in float, the old-phi rows prefetched as doubles
+// (32-B dbl4 accesses), phi' = phi + (double)(tau / n) (double)U, phi_bar and the sums of the 4 points in double.
+// The fp32 / fp64 kernel keeps its own text, so its code and results stay the parent's bit for bit.
+template <int N, int RW, int NT, int PF, typename R, bool G16, typename P = R>
+__device__ __forceinline__ void invy_update_fast_body(const KP<R>& p, const PhiX<R, P>& px,
+                                                      const cplx<R>* __restrict__ twy) {
+  using C = cplx<R>;
+  using V = V4<R>;
+  using VP = V4<P>;
+  constexpr int NL = RW / 2;
+  constexpr int GPT = (N / 4) / NT;
+  if (p.ctrl->done) return;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  C* A = reinterpret_cast<C*>(smem_raw);
+  R* Af = reinterpret_cast<R*>(A);
+  constexpr bool TWL = N <= 4096;   // twiddle seeds in LDS (see k_res_fwdy_fused_2d)
+  C* twl = A + NL * Pad<N>::LINE;
+  if constexpr (TWL) fill_twlds<C, N>(twl, twy, 1, G16 ? 48 : TwLds<N>::SIZE);
+  const int nx = p.nx, B = p.B, nb = p.nb;
+  const int ngx = nx / RW;
+  const int ntask = ngx * p.T;
+  const size_t plane = (size_t)nx * N;
+  const R scale = p.tau * p.inv_n;
+  const int CS4 = RW * B / 4;
+  const int lB = p.lB;
+  const int lCS4 = lB + (RW == 8 ? 1 : RW == 4 ? 0 : RW == 2 ? -1 : -2);   // log2(CS4), B power of two
+  const int tid = threadIdx.x;
+  constexpr int NLD = RW * N / 4 / NT, BATCH = NLD < 8 ? NLD : 8;
+  static_assert((RW * N / 4) % NT == 0 && NLD % BATCH == 0, "whole spectrum batches per thread");
+  double s[3] = {0.0, 0.0, 0.0};
+  // Per task: the spectrum goes to LDS, the first old-phi row pair is issued, and the transform runs on
+  // LDS only (twiddle seeds in LDS), so that pair stays in flight across it; each pair prefetches the next.
+  for (int task = xcd_remap(blockIdx.x, gridDim.x); task < ntask; task += gridDim.x) {
+    const int j = task / ngx;
+    const int x0 = (task - j * ngx) * RW;
+    if (x0 + RW <= p.xl0 || x0 >= p.xl1) continue;   // x-slab padding / ghost rows only (workgroup-uniform)
+    const R* wk = p.work + (size_t)j * nb * nx * B;
+    // the task's spectrum (RW*B/4 float4 per block, N/B blocks = NLD per thread), in batches of up to 8
+    // loads issued together: one memory round trip per batch, not per float4.  The thread index is
+    // laundered per task so the 4*BATCH LDS addresses are not hoisted out of the task loop (registers).
+    int tl = tid;
+    asm volatile("" : "+v"(tl));
+    if (RW == 2 && B == 1) {   // fp64 C4 (half-real spectrum): chunk b = rows x0, x0+1 at ky = b, one 16-B load
+      constexpr int NC = N / NT, CB = NC < 8 ? NC : 8;
+#pragma unroll
+      for (int i0 = 0; i0 < NC; i0 += CB) {
+        C v[CB];
+#pragma unroll
+        for (int i = 0; i < CB; ++i) v[i] = *reinterpret_cast<const C*>(wk + (size_t)(tl + (i0 + i) * NT) * nx + x0);
+#pragma unroll
+        for (int i = 0; i < CB; ++i) A[pix(tl + (i0 + i) * NT)] = v[i];
+      }
+    } else
+#pragma unroll
+    for (int i0 = 0; i0 < NLD; i0 += BATCH) {
+      V v[BATCH];
+#pragma unroll
+      for (int i = 0; i < BATCH; ++i) {
+        const int t = tl + (i0 + i) * NT;
+        v[i] = (p.dbg & 512) ? ld4(wk + (size_t)x0 * N + 4 * t)   // PDHG_DBG 512: task-contiguous (timing)
+                             : ld4(wk + ((size_t)(t >> lCS4) * nx + x0) * B + (t & (CS4 - 1)) * 4);
+      }
+#pragma unroll
+      for (int i = 0; i < BATCH; ++i) {
+        const int t = tl + (i0 + i) * NT;
+        const int b = t >> lCS4, part = t & (CS4 - 1);
+        if (B == 2) {   // the float4 holds rows r, r+1 (r = 2 part) at columns 2b, 2b+1: two complex elements
+          C* Al = A + part * Pad<N>::LINE;
+          Al[pix(2 * b)] = cmk<C>(v[i].x, v[i].z);
+          Al[pix(2 * b + 1)] = cmk<C>(v[i].y, v[i].w);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int f = part * 4 + e;
+            const int r = f >> lB, c = f & (B - 1);
+            Af[((r >> 1) * Pad<N>::LINE + pix(b * B + c)) * 2 + (r & 1)] = f4(v[i], e);
+          }
+        }
+      }
+    }
+    P* phi = phi_of(p, px) + (size_t)(j + 1) * plane;
+    P* pbar = phibar_of(p, px) + (size_t)(j + 1) * plane;
+    // old-phi row pairs, one per step s = gi * NL + l; PF steps in flight ahead of the one being updated
+    // (step 0 before the transform, steps 1 .. PF-1 right after it, when the FFT's registers are free)
+    constexpr int NS = GPT * NL;
+    VP op[NS][2];
+    auto ldstep = [&](int s) {
+      const size_t idx = (size_t)(x0 + 2 * (s % NL)) * N + 4 * (tid + (s / NL) * NT);
+      op[s][0] = ld4(phi + idx);
+      op[s][1] = ld4(phi + idx + N);
+    };
+    ldstep(0);
+    lds_sync();
+    if (!(p.dbg & 64)) {   // timing experiments only (PDHG_DBG): 64 skips the transform
+      if constexpr (TWL && G16) lds_fft_inplace_tl16<C, N, NL, NT, Pad<N>::LINE>(A, twl, twy);
+      else if constexpr (TWL) lds_fft_inplace_tl<C, N, NL, NT, Pad<N>::LINE>(A, twl);
+      else lds_fft_inplace<C, N, NL, NT>(A, twy);
+    }
+#pragma unroll
+    for (int s = 1; s < PF && s < NS; ++s) ldstep(s);
+#pragma unroll
+    for (int gi = 0; gi < GPT; ++gi) {
+      const int y = 4 * (tid + gi * NT);
+#pragma unroll
+      for (int l = 0; l < NL; ++l) {   // rows 2l (real part) and 2l+1 (imaginary part) of line l
+        const int st = gi * NL + l;
+        const VP o4[2] = {op[st][0], op[st][1]};
+        if (st + PF < NS) ldstep(st + PF);
+        const C* Z = A + l * Pad<N>::LINE;
+        V u[2];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          R a, b2;
+          hartley_padded<C, R>(Z, N, y + e, a, b2);
+          f4set(u[0], e, a);
+          f4set(u[1], e, b2);
+        }
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          const int xr = x0 + 2 * l + h;
+          if (xr < p.xl0 || xr >= p.xl1) continue;   // x-slab ghost row (workgroup-uniform)
+          const size_t idx = (size_t)xr * N + y;
+          VP nw, pb;
+          P fs[3] = {(P)0, (P)0, (P)0};   // the 4 points in P (fp32: then one fp64 add per sum)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const P o = f4(o4[h], e);
+            const P n = o + (P)scale * (P)f4(u[h], e);
+            f4set(nw, e, n);
+            f4set(pb, e, (P)2 * n - o);
+            const P d = n - o;
+            fs[0] = fmar(d, d, fs[0]);
+            fs[1] = fmar(o, o, fs[1]);
+            fs[2] = fmar(n, n, fs[2]);
+          }
+#pragma unroll
+          for (int i = 0; i < 3; ++i) s[i] += (double)fs[i];
+          st4(phi + idx, nw);
+          st4(pbar + idx, pb);
+        }
+      }
+    }
+    lds_sync();
+  }
+  block_reduce_store<3>(s, p.partials, blockIdx.x);
+}
 template <int N, int RW, int NT, int PF = 1, typename R = float, bool G16 = false>
 __global__ void __launch_bounds__(NT) k_invy_update_fast_2d(KP<R> p, const cplx<R>* __restrict__ twy) {
   using C = cplx<R>;
@@ -701,6 +848,11 @@ __global__ void __launch_bounds__(NT) k_invy_update_fast_2d(KP<R> p, const cplx<
     lds_sync();
   }
   block_reduce_store<3>(s, p.partials, blockIdx.x);
+}
+template <int N, int RW, int NT, int PF = 1>
+__global__ void __launch_bounds__(NT) k_invy_update_fast_mixed_2d(KP<float> p, const float2* __restrict__ twy,
+                                                                  PhiX<float, double> px) {
+  invy_update_fast_body<N, RW, NT, PF, float, false, double>(p, px, twy);
 }
 
 }  // namespace pdhg
@@ -1273,6 +1425,126 @@ __global__ void __launch_bounds__(512) k_precond_xt_ws_2d(KP<float> p, const flo
 // ONE: every workgroup has exactly one time row (jchunk == 1, e.g. the T = 1 marching windows): the row is loaded
 // once, with no prefetch registers (the marching form re-loads its last row to stay branch-free), the same arithmetic.
 // ONE = 2: the same with 4 waves per SIMD asked of the compiler (fp64: 128 VGPRs + 28 B of spill, A/B only).
+// dual_fast_body<.., P>: k_dual_fast_2d (below) with phi_bar in P, for the mixed context's k_dual_fast_mixed_2d: the
+// centre, the x neighbours, the wave-edge y neighbours and row j loaded as doubles, the y neighbours crossing lanes as
+// doubles, the phi_bar terms of a point in double and rounded to float once (dual_point_x), rho / alp and the sums as
+// in fp32.  The fp32 / fp64 kernel keeps its own text (as k_invy_update_fast_2d).
+template <int EGNO, typename R, int ONE, typename P = R>
+__device__ __forceinline__ void dual_fast_body(const KP<R>& p, const PhiX<R, P>& px, int jchunk, int jbase, int jend,
+                                               int zbase) {
+  using V = V4<R>;
+  using VP = V4<P>;
+  const P* const phibar = phibar_of(p, px);
+  if (p.ctrl->done || p.ctrl->inner_done) return;
+  constexpr int NA = (EGNO == 3) ? 2 : 4;
+  constexpr int NS = 3 + 3 * NA;
+  const int cur = p.ctrl->cur;
+  const int src_set = (p.inplace || p.sub == 0) ? cur : 1 - cur;
+  const int dst_set = p.inplace ? cur : 1 - cur;
+  const int nx = p.nx, ny = p.ny;
+  const size_t plane = (size_t)nx * ny;
+  const int x = xcd_remap(blockIdx.x, gridDim.x);
+  const bool live = x >= p.xl0 && x < p.xl1;   // workgroup-uniform (x-slab ghost / padding rows: not stored or summed)
+  const int y = 4 * (blockIdx.y * blockDim.x + threadIdx.x);
+  // rows [jbase, jend) in chunks of jchunk (blockIdx.z); partials of this launch start at block row zbase
+  const int j0 = jbase + blockIdx.z * jchunk;
+  const int j1 = min(jend, j0 + jchunk);
+  double s[NS];
+#pragma unroll
+  for (int i = 0; i < NS; ++i) s[i] = 0.0;
+  if (y < ny) {
+    const int yw0 = __builtin_amdgcn_readfirstlane(y);
+    const int ywm = nb_index(yw0 - 1, ny, p.bcy), ywp = nb_index(yw0 + 4 * kWave, ny, p.bcy);
+    const bool zym = ywm < 0, zyp = ywp < 0;
+    const int ywmc = zym ? 0 : ywm, ywpc = zyp ? 0 : ywp;
+    const int xm = nb_index(x - 1, nx, p.bcx), xp = nb_index(x + 1, nx, p.bcx);
+    const bool zxm = xm < 0, zxp = xp < 0;
+    const size_t rxm = (size_t)(zxm ? x : xm) * ny, rxc = (size_t)x * ny, rxp = (size_t)(zxp ? x : xp) * ny;
+    const V ay4 = ld4(p.ay + y);
+    const R axc = p.ax[x];
+    const R* rs = p.rho[src_set];
+    R* rd = p.rho[dst_set];
+    const R* as[NA];
+    R* ad[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      as[a] = p.alp[src_set][a];
+      ad[a] = p.alp[dst_set][a];
+    }
+    struct In {
+      VP pm, pc, pp;
+      V rho, al[NA];
+      P el, er;
+    };
+    auto load = [&](int j) {
+      In in;
+      const P* f1 = phibar + (size_t)(j + 1) * plane;
+      in.pm = ld4(f1 + rxm + y);
+      in.pc = ld4(f1 + rxc + y);
+      in.pp = ld4(f1 + rxp + y);
+      in.el = f1[rxc + ywmc];
+      in.er = f1[rxc + ywpc];
+      const size_t o = (size_t)j * plane + rxc + y;
+      in.rho = ld4(rs + o);
+#pragma unroll
+      for (int a = 0; a < NA; ++a) in.al[a] = ld4(as[a] + o);
+      return in;
+    };
+    VP f0 = ld4(phibar + (size_t)j0 * plane + rxc + y);   // phi_bar row j
+    auto step = [&](int j, const In& in) {
+      const VP pm = zxm ? z4r<P>() : in.pm, pp = zxp ? z4r<P>() : in.pp, pc = in.pc;
+      const P pyl = lane_from_prev(pc.w, zym ? (P)0 : in.el);
+      const P pyr = lane_from_next(pc.x, zyp ? (P)0 : in.er);
+      V rn4, an4[NA];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const P c = f4(pc, e);
+        const P lft = e == 0 ? pyl : f4(pc, e - 1);
+        const P rgt = e == 3 ? pyr : f4(pc, e + 1);
+        R ao[4], an[4];
+#pragma unroll
+        for (int a = 0; a < NA; ++a) ao[a] = f4(in.al[a], e);
+        const R rho = f4(in.rho, e);
+        const R rn = dual_point_x<R, EGNO, P>(p, px, c, f4(pm, e), f4(pp, e), lft, rgt, f4(f0, e), rho, ao, axc,
+                                              f4(ay4, e), an);
+        f4set(rn4, e, rn);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) f4set(an4[a], e, an[a]);
+        if (!live) continue;
+        const double dr = (double)rn - (double)rho;
+        s[0] += dr * dr;
+        s[1] += (double)rn * (double)rn;
+        s[2] += (double)rho * (double)rho;
+#pragma unroll
+        for (int a = 0; a < NA; ++a) {
+          const double da = (double)an[a] - (double)ao[a];
+          s[3 + 3 * a] += da * da;
+          s[4 + 3 * a] += (double)an[a] * (double)an[a];
+          s[5 + 3 * a] += (double)ao[a] * (double)ao[a];
+        }
+      }
+      const size_t o = (size_t)j * plane + rxc + y;
+      if (live) {
+        st4(rd + o, rn4);
+#pragma unroll
+        for (int a = 0; a < NA; ++a) st4(ad[a] + o, an4[a]);
+      }
+      f0 = pc;
+    };
+    if constexpr (ONE) {   // one row per workgroup: no next-row prefetch (half the input registers)
+      step(j0, load(j0));
+    } else {
+      In nxt = load(j0);
+#pragma unroll 1
+      for (int j = j0; j < j1; ++j) {
+        const In in = nxt;
+        nxt = load(min(j + 1, j1 - 1));   // (the last step reloads its own row: keeps the loop branch-free)
+        step(j, in);
+      }
+    }
+  }
+  block_reduce_store<NS>(s, p.partials, ((zbase + (int)blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+}
 template <int EGNO, typename R = float, int ONE = 0>
 __global__ void __launch_bounds__(256, ONE == 2 ? 4 : 1) k_dual_fast_2d(KP<R> p, int jchunk, int jbase, int jend, int zbase) {
   using V = V4<R>;
@@ -1384,6 +1656,11 @@ __global__ void __launch_bounds__(256, ONE == 2 ? 4 : 1) k_dual_fast_2d(KP<R> p,
     }
   }
   block_reduce_store<NS>(s, p.partials, ((zbase + (int)blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+}
+template <int EGNO, int ONE = 0>
+__global__ void __launch_bounds__(256) k_dual_fast_mixed_2d(KP<float> p, int jchunk, int jbase, int jend, int zbase,
+                                                            PhiX<float, double> px) {
+  dual_fast_body<EGNO, float, ONE, double>(p, px, jchunk, jbase, jend, zbase);
 }
 
 }  // namespace pdhg

@@ -63,6 +63,32 @@ struct KP {
   int b0;
 };
 
+// Mixed precision (pdhg_problem.precision 12): the state and every table are R = float, phi and phi_bar P = double.
+// The mixed forms of the kernels that read or write phi / phi_bar (k_*_mixed_2d) take this block as one extra
+// argument: the double pointer pair (KP<float>::phi / phibar stay null) and the reciprocals and epsl of the phi_bar
+// terms of the dual (dual_pre<double>) formed from the problem's doubles, not widened from KP's floats.
+// P == R: empty, the kernels read KP.
+template <typename R, typename P = R>
+struct PhiX {};
+template <>
+struct PhiX<float, double> {
+  double* phi;             // [T+1][nx][ny]
+  double* phibar;          // [T+1][nx][ny]
+  double inv_dx, inv_dy, inv_dt, inv_dx2, inv_dy2, epsl;
+};
+template <typename R>
+__device__ __forceinline__ R* phi_of(const KP<R>& p, const PhiX<R, R>&) { return p.phi; }
+template <typename R>
+__device__ __forceinline__ R* phibar_of(const KP<R>& p, const PhiX<R, R>&) { return p.phibar; }
+__device__ __forceinline__ double* phi_of(const KP<float>&, const PhiX<float, double>& x) { return x.phi; }
+__device__ __forceinline__ double* phibar_of(const KP<float>&, const PhiX<float, double>& x) { return x.phibar; }
+// whose inv_dx ... epsl the phi_bar terms use
+template <typename R>
+__device__ __forceinline__ const KP<R>& pre_coef(const KP<R>& p, const PhiX<R, R>&) { return p; }
+__device__ __forceinline__ const PhiX<float, double>& pre_coef(const KP<float>&, const PhiX<float, double>& x) {
+  return x;
+}
+
 // neighbour index along an axis of length n with boundary condition bc
 // (utils_diff_op.py:5-7): returns -1 when the value is a Dirichlet zero.
 __device__ __forceinline__ int nb_index(int i, int n, int bc) {

@@ -17,6 +17,9 @@ namespace pdhg {
 
 constexpr size_t kLdsBytes = 160 * 1024;
 constexpr int kMultiSub = 5;    // sub-iterations one chunk pass of the dual loop runs (kernels_dual_multi.hpp)
+// mixed update at 512 threads: old-phi row pairs (doubles) in flight; 238 VGPRs, no spill at 4 (fp32: 228), the same
+// 2 waves per SIMD at 1 .. 4, so the fp32 default depth
+constexpr int kMixedUpdPF = 4;
 constexpr int kFoldRows = 64;   // rows of the first fold level (k_fold_partials) after the partial table
 
 inline FFTPlan make_plan(int n, bool& ok) {
@@ -44,11 +47,13 @@ struct Decomp {
   int j0 = 0, Tg = 0;
   bool xslab = false;   // x-slab: global x rows [rank * nloc, (rank + 1) * nloc) of nxg; pb.nx = nloc + 16 local rows
   int rank = 0, P = 1, nxg = 0, nloc = 0;
+  bool mixed = false;   // precision 12: S = 4 with phi and phi_bar in double (single 2-D contexts)
 };
 
 struct PathPlan {
   FFTPlan plx{}, ply{};   // x (global length) and y line transforms
   int na = 0, n_dead = 0;
+  bool mixed = false;     // fp32 state and kernels, phi / phi_bar double (the mixed update and dual kernels)
   bool two_sets = false;  // rho_alp_iters > 1: two (rho, alp) buffer sets
   // spectral blocks (KP::B / lB / nb / half_real / tile_j)
   int B = 1, lB = 0, nb = 1, tile_j = 0;
@@ -114,8 +119,8 @@ struct PathPlan {
   bool thomas_chunk = false;      // t-solve in chunks of rows (k_thomas_chunk_1d)
 };
 
-// S = sizeof(real) (4 / 8).  pb is the context's own problem (an x-slab's has its local rows).  Returns PDHG_OK, or
-// PDHG_ERR_UNSUPPORTED with the reason in err.
+// S = sizeof(real) (4 / 8; a mixed context plans as S = 4 with dc.mixed).  pb is the context's own problem (an
+// x-slab's has its local rows).  Returns PDHG_OK, or PDHG_ERR_UNSUPPORTED with the reason in err.
 inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tuning& tn, PathPlan& pl,
                       std::string& err) {
   auto fail = [&err](int code, const char* fmt, auto... args) {
@@ -129,6 +134,9 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     return code;
   };
   pl = PathPlan{};
+  if (dc.mixed && (S != 4 || pb.ndim != 2 || dc.slab || dc.xslab))
+    return fail(PDHG_ERR_UNSUPPORTED, "mixed precision (12) is implemented for single 2-D contexts only");
+  pl.mixed = dc.mixed;
   const int nx = pb.nx, ny = pb.ny, T = pb.T;
   const int nxg = dc.xslab ? dc.nxg : nx;   // length of the x transform (global nx for an x-slab)
   const bool is2d = pb.ndim == 2, slab = dc.slab, xslab = dc.xslab;
@@ -263,6 +271,8 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
         const int v = *tn.dual_rx;
         if (v == 0 || (((S == 4 && (v == 4 || v == 16)) || v == 8) && nx % v == 0)) pl.dual_rx = v;
       }
+      // mixed: the row-per-thread sweep (k_dual_lds_2d stages phi_bar rows through LDS in R), hence no fused residual
+      if (dc.mixed) pl.dual_rx = 0;
       if (S == 8 && pl.dual_rx == 8 && tn.dual_ypl.value_or(0) == 2) pl.dual_ypl = 2;
       dual_one = tn.dual_one;
       pl.NTd = pl.dual_rx ? pl.dual_rx * 64 : std::min(256, ny / 4);
@@ -432,6 +442,7 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
 // the creation-time keys of pdhg_path_info / pdhg_plan_info (S = sizeof(real), ny / nx: the context's own)
 inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const std::string& k, int* value) {
   if (k == "fused_residual") *value = pl.fuse_res ? 1 : 0;
+  else if (k == "mixed") *value = pl.mixed ? 1 : 0;   // precision 12; the other keys: the fp32 kernels chosen
   else if (k == "fast_rows") *value = pl.fast_rows ? 1 : 0;
   else if (k == "res64") *value = pl.res64 ? 1 : 0;
   else if (k == "dual_multi") *value = pl.dual_multi ? 1 : 0;   // rho_alp_iters > 1: chunked dual passes

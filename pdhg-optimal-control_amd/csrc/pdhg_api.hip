@@ -46,6 +46,8 @@ namespace {
 constexpr uint32_t kCtxMagic = 0x50444843u;    // "PDHC"
 constexpr uint32_t kMultiMagic = 0x5044484du;  // "PDHM"
 
+constexpr int kMixedPrecision = 12;   // pdhg_problem.precision: fp32 state, fp64 phi / phi_bar (single 2-D contexts)
+
 struct CtxBox {
   uint32_t magic = kCtxMagic;
   int precision;
@@ -67,6 +69,7 @@ int dispatch(pdhg_ctx* ctx, F&& f) {
   CtxBox* b = ctx_box(ctx);
   if (!b) return fail(PDHG_ERR_ARG, "null or foreign context handle");
   if (b->precision == 8) return f(*static_cast<Impl<double>*>(b->impl.get()));
+  if (b->precision == kMixedPrecision) return f(*static_cast<Impl<float, double>*>(b->impl.get()));
   return f(*static_cast<Impl<float>*>(b->impl.get()));
 }
 
@@ -128,7 +131,10 @@ int validate_problem(const pdhg_problem& p) {
   if (p.T < 1) return fail(PDHG_ERR_ARG, "T must be >= 1");
   if (!(p.dx > 0) || !(p.dt > 0) || (p.ndim == 2 && !(p.dy > 0))) return fail(PDHG_ERR_ARG, "grid spacings must be > 0");
   if (!p.xs || (p.ndim == 2 && !p.ys)) return fail(PDHG_ERR_ARG, "grid coordinates required");
-  if (p.precision != 4 && p.precision != 8) return fail(PDHG_ERR_ARG, "precision must be 4 or 8");
+  if (p.precision != 4 && p.precision != 8 && p.precision != kMixedPrecision)
+    return fail(PDHG_ERR_ARG, "precision must be 4, 8 or 12 (mixed)");
+  if (p.precision == kMixedPrecision && p.ndim != 2)
+    return fail(PDHG_ERR_UNSUPPORTED, "mixed precision (12) is implemented for 2-D contexts only");
   if (p.rho_alp_iters < 1) return fail(PDHG_ERR_ARG, "rho_alp_iters must be >= 1");
   // preconditioner boundary conditions (utils_precond.py:121-124, :157-163)
   if (p.ndim == 1 && p.bc_x != 0) return fail(PDHG_ERR_UNSUPPORTED, "H1_precond_1d supports bc=0 only");
@@ -173,6 +179,12 @@ int pdhg_create(const pdhg_problem* prob, int device, pdhg_ctx** out) {
   box->precision = p.precision;
   if (p.precision == 8) {
     auto im = std::make_unique<Impl<double>>();
+    im->pb = p;
+    im->device = device;
+    rc = im->setup();
+    box->impl = std::move(im);
+  } else if (p.precision == kMixedPrecision) {
+    auto im = std::make_unique<Impl<float, double>>();
     im->pb = p;
     im->device = device;
     rc = im->setup();
@@ -284,8 +296,11 @@ int pdhg_plan_info(const pdhg_problem* prob, const char* key, int* value) {
   if ((rc = validate_problem(*prob))) return rc;
   PathPlan pl;
   std::string why;
-  if ((rc = plan_paths(*prob, prob->precision, Decomp{}, Tuning::from_env(), pl, why))) return fail(rc, "%s", why.c_str());
-  if (plan_key(pl, *prob, prob->precision, key, value)) return PDHG_OK;
+  Decomp dc{};
+  dc.mixed = prob->precision == kMixedPrecision;
+  const int S = dc.mixed ? 4 : prob->precision;   // a mixed context plans as fp32
+  if ((rc = plan_paths(*prob, S, dc, Tuning::from_env(), pl, why))) return fail(rc, "%s", why.c_str());
+  if (plan_key(pl, *prob, S, key, value)) return PDHG_OK;
   return fail(PDHG_ERR_ARG, "path key %s is unknown or a runtime counter of a context", key);
 }
 int pdhg_profile_enable(pdhg_ctx* ctx, int enable) {
@@ -328,6 +343,8 @@ int pdhg_create_slab(const pdhg_problem* prob, int j0, int T_total, int device, 
   if (j0 < 0 || prob->T < 1 || j0 + prob->T > T_total)
     return fail(PDHG_ERR_ARG, "slab rows [%d, %d) outside the window of %d rows", j0, j0 + prob->T, T_total);
   if (prob->ndim != 2) return fail(PDHG_ERR_UNSUPPORTED, "t-slab decomposition is 2-D only");
+  if (prob->precision == kMixedPrecision)
+    return fail(PDHG_ERR_UNSUPPORTED, "mixed precision (12) is implemented for single contexts only (no t-slab)");
   // validate the rest exactly like pdhg_create, then rebuild as a slab (fp32, or fp64 = the reference's arithmetic,
   // jaxsrc/update_fns_in_pdhg.py:10)
   pdhg_ctx* probe = nullptr;
@@ -445,6 +462,8 @@ int pdhg_create_xslab(const pdhg_problem* prob, int rank, int nranks, int device
   *out = nullptr;
   if (nranks < 1 || rank < 0 || rank >= nranks) return fail(PDHG_ERR_ARG, "rank %d of %d", rank, nranks);
   if (prob->ndim != 2) return fail(PDHG_ERR_UNSUPPORTED, "x-slab decomposition is 2-D only");
+  if (prob->precision == kMixedPrecision)
+    return fail(PDHG_ERR_UNSUPPORTED, "mixed precision (12) is implemented for single contexts only (no x-slab)");
   // bc (0,0), or egno 3's (1,0): Neumann x edges -- the first / last slab's outer ghost row replicates its own edge
   // row (nb_index bc 1), the transposed x lines take the DCT of the generic x kernel
   if (prob->bc_y != 0 || (prob->bc_x != 0 && prob->bc_x != 1))

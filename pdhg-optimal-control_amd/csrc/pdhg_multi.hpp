@@ -553,6 +553,8 @@ extern "C" {
 int pdhg_create_multi(const pdhg_problem* prob, const int* devices, int ndev, pdhg_multi** out) {
   if (!prob || !devices || !out || ndev < 1) return fail(PDHG_ERR_ARG, "null argument or ndev < 1");
   *out = nullptr;
+  if (prob->precision == kMixedPrecision)
+    return fail(PDHG_ERR_UNSUPPORTED, "mixed precision (12) is implemented for single contexts only (no multi-device)");
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess || n == 0) return fail(PDHG_ERR_HIP, "no HIP device available");
   for (int r = 0; r < ndev; ++r)

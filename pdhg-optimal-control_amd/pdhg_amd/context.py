@@ -32,7 +32,8 @@ class PDHGContext:
         prob = N.pdhg_problem()
         prob.egno, prob.ndim, prob.bc_x, prob.bc_y = self.egno, self.ndim, int(bcx), int(bcy)
         prob.nx, prob.ny, prob.T = self.nx, self.ny, self.T
-        prob.precision = {"fp32": 4, "fp64": 8, 4: 4, 8: 8}[precision]
+        # "mixed" (12): fp32 state with fp64 phi / phi_bar; single 2-D contexts only (the subclasses refuse it)
+        prob.precision = {"fp32": 4, "fp64": 8, "mixed": 12, 4: 4, 8: 8, 12: 12}[precision]
         prob.rho_alp_iters = int(rho_alp_iters)
         prob.dx, prob.dy, prob.dt = float(dx), float(dy if ndim == 2 else 0.0), float(dt)
         prob.epsl, prob.c_on_rho = float(epsl), float(c_on_rho)
@@ -41,6 +42,8 @@ class PDHGContext:
         prob.ys = N.dptr(self._ys) if self._ys is not None else None
         self.rho_alp_iters = int(rho_alp_iters)
         self._prob = prob
+        if prob.precision == 12 and type(self)._create is not PDHGContext._create:
+            raise ValueError("precision 'mixed' is implemented for the single context (PDHGContext) only")
         self._h = self._create(prob, int(device))
         self._version = 0         # bumped by every call that changes the device state
         self._resident = None     # (version, rho, alp): host arrays known to equal the device's rho / alp

@@ -21,6 +21,8 @@ from . import _native as N
 class MultiContext:
     def __init__(self, egno, nx, ny, T, dx, dy, dt, xs, ys, devices=(0, 0), epsl=0.0, c_on_rho=70.0,
                  precision="fp32", rho_alp_iters=1):
+        if precision in ("mixed", 12):
+            raise ValueError("precision 'mixed' is implemented for the single context (PDHGContext) only")
         if precision not in ("fp32", "fp64", 4, 8):
             raise ValueError("precision must be fp32 or fp64")
         self._lib = N.load()

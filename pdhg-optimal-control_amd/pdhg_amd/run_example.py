@@ -10,7 +10,7 @@ npz tree (pdhg_amd.solver) instead of a pickle.  --plot writes the reference's f
 component, their sum; matplotlib, PNG) under plots/<stamp>/eg<egno>_<ndim>d, and with --plot_traj_num_1d > 0
 simulates the controlled trajectories from the solved alp (pdhg_amd.trajectories, run_example.py:342-393)
 and saves them as traj_<prefix>.npz (+ figures).  --tfboard is accepted and ignored (no TensorBoard).
-Extra flags: --precision {fp32,fp64}, --rho_alp_iters (the reference fixes 10), --out (root dir),
+Extra flags: --precision {fp32,fp64,mixed}, --rho_alp_iters (the reference fixes 10), --out (root dir),
 --load_middle / --load_middle_timestamp (resume from middle results, run_example.py:246-248).
 """
 import argparse
@@ -59,7 +59,7 @@ def build_parser():
     A("--Ct", type=float, default=1.0)
     A("--numerical_L_ind", type=int, default=0)
     # this build
-    A("--precision", choices=("fp32", "fp64"), default="fp64",
+    A("--precision", choices=("fp32", "fp64", "mixed"), default="fp64",
       help="device arithmetic (the reference runs float64)")
     A("--rho_alp_iters", type=int, default=10)
     A("--out", default=".")

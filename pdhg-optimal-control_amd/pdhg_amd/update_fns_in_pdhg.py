@@ -7,8 +7,10 @@ device-resident loop in ``utils_pdhg_solver`` instead: per-call use moves the
 whole state over PCIe twice.
 
 Precision: float64 by default, as the reference (jax_enable_x64, update_fns_in_pdhg.py:10), so a caller
-swapping these in for the reference's functions gets its arithmetic; ``set_precision("fp32")`` (or
-``make_update_fns(..., precision="fp32")``) selects the fp32 fast kernels the benchmark runs.
+swapping these in for the reference's functions gets its arithmetic.  ``set_precision("fp32")`` selects the fp32
+throughput kernels (which miss the 1e-5 parity bound at epsl = 0.1 on fine grids), ``set_precision("mixed")`` the
+fp32 kernels with phi and phi_bar held in float64 (2-D only).  ``make_update_fns(..., precision=...)`` selects the
+same per function pair; the benchmark's default is fp64.
 """
 import numpy as np
 
@@ -20,7 +22,7 @@ _CACHE_MAX = 4
 
 
 def set_precision(p):
-    assert p in ("fp32", "fp64")
+    assert p in ("fp32", "fp64", "mixed")
     _PRECISION[0] = p
 
 
@@ -112,38 +114,43 @@ def check_fv(fv, ndim, space, dspatial, bc):
 
 
 # ---- primal ----
-def _primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, epsl, x_arr, bc, C, pow, Ct):
+def _primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, epsl, x_arr, bc, C, pow, Ct,
+            precision=None):
     spec = _spec(fns_dict)
     phi_prev = np.asarray(phi_prev, dtype=np.float64)
     T = phi_prev.shape[0] - 1
-    ctx = get_context(spec, T, phi_prev.shape[1:], dt, dspatial, epsl, x_arr, bc, C, pow, Ct, c_on_rho)
+    ctx = get_context(spec, T, phi_prev.shape[1:], dt, dspatial, epsl, x_arr, bc, C, pow, Ct, c_on_rho,
+                      precision=precision)
     ctx.set_state(phi_prev, rho_prev, alp_prev)
     ctx.update_primal(tau)
     return ctx.get_state()[0]
 
 
 def update_primal_1d(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, fv, epsl, x_arr, t_arr, bc,
-                     C=1.0, pow=1, Ct=1):
+                     C=1.0, pow=1, Ct=1, precision=None):
     """phi + tau * H1^{-1} cont_residual (update_fns_in_pdhg.py:135-140); fv must be the stencil's symbol
     (check_fv), which the kernels form analytically."""
     check_fv(fv, 1, np.shape(phi_prev)[1:], dspatial, bc)
-    return _primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, epsl, x_arr, bc, C, pow, Ct)
+    return _primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, epsl, x_arr, bc, C, pow, Ct,
+                   precision)
 
 
 def update_primal_2d(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, fv, epsl, x_arr, t_arr, bc,
-                     C=1.0, pow=1, Ct=1):
+                     C=1.0, pow=1, Ct=1, precision=None):
     """update_fns_in_pdhg.py:142-147 (pow and Ct are ignored in 2-D, as in the reference); fv as update_primal_1d."""
     check_fv(fv, 2, np.shape(phi_prev)[1:], dspatial, bc)
-    return _primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, epsl, x_arr, bc, C, 1.0, 1.0)
+    return _primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, epsl, x_arr, bc, C, 1.0, 1.0,
+                   precision)
 
 
 # ---- dual ----
-def _dual(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict, x_arr, bc, iters, eps):
+def _dual(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict, x_arr, bc, iters, eps,
+          precision=None):
     spec = _spec(fns_dict)
     phi_bar = np.asarray(phi_bar, dtype=np.float64)
     T = phi_bar.shape[0] - 1
     ctx = get_context(spec, T, phi_bar.shape[1:], dt, dspatial, epsl, x_arr, bc, c_on_rho=c_on_rho,
-                      rho_alp_iters=iters)
+                      rho_alp_iters=iters, precision=precision)
     ctx.set_state(None, rho_prev, alp_prev)
     ctx.set_phi_bar(phi_bar)
     used = ctx.update_dual(sigma, eps, iters)
@@ -152,16 +159,16 @@ def _dual(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_
 
 
 def update_dual_oneiter(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, x_arr, t_arr, bc, fns_dict,
-                        ndim):
+                        ndim, precision=None):
     """One alpha/rho prox step and its error (update_fns_in_pdhg.py:150-165)."""
     rho, alp, _, ctx = _dual(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict, x_arr, bc,
-                             1, -np.inf)
+                             1, -np.inf, precision)
     return rho, alp, ctx.inner_error()
 
 
 def update_dual_alternative(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict, x_arr, t_arr,
-                            ndim, bc, rho_alp_iters=10, eps=1e-7):
+                            ndim, bc, rho_alp_iters=10, eps=1e-7, precision=None):
     """<= rho_alp_iters sub-iterations with early exit at err < eps (update_fns_in_pdhg.py:167-180)."""
     rho, alp, _, _ = _dual(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict, x_arr, bc,
-                           rho_alp_iters, eps)
+                           rho_alp_iters, eps, precision)
     return rho, alp

@@ -16,17 +16,19 @@ from .solver import save
 
 
 def make_update_fns(ndim, bc, C=1.0, pow=1.0, Ct=1.0, rho_alp_iters=10, precision=None):
-    """fn_update_primal / fn_update_dual as bound in solve_HJ (run_example.py:192-203), tagged for the device loop."""
+    """fn_update_primal / fn_update_dual as bound in solve_HJ (run_example.py:192-203), tagged for the device loop.
+    precision: "fp32", "fp64", "mixed" (2-D), or None for update_fns_in_pdhg's current default."""
     upd_primal = U.update_primal_1d if ndim == 1 else U.update_primal_2d
 
     def fn_update_primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, fv, epsl, x_arr, t_arr):
         return upd_primal(phi_prev, rho_prev, c_on_rho, alp_prev, tau, dt, dspatial, fns_dict, fv, epsl, x_arr, t_arr,
-                          bc, C=C, pow=pow, Ct=Ct)
+                          bc, C=C, pow=pow, Ct=Ct, precision=precision)
 
     def fn_update_dual(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict, x_arr, t_arr, nd,
                        eps):
         return U.update_dual_alternative(phi_bar, rho_prev, c_on_rho, alp_prev, sigma, dt, dspatial, epsl, fns_dict,
-                                         x_arr, t_arr, nd, bc, rho_alp_iters=rho_alp_iters, eps=eps)
+                                         x_arr, t_arr, nd, bc, rho_alp_iters=rho_alp_iters, eps=eps,
+                                         precision=precision)
 
     tag = {"bc": bc, "C": C, "pow": pow, "Ct": Ct, "rho_alp_iters": rho_alp_iters, "precision": precision}
     fn_update_primal._pdhg_native = tag
