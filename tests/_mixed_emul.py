@@ -56,10 +56,12 @@ def start_state(P, variant, phi=None, rho=None, alp=None):
     return (phi.astype(F64 if variant == "mixed" else F32), rho.astype(F32), tuple(a.astype(F32) for a in alp))
 
 
-def run(P, variant, iters, k=1, eps=-1.0, state=None, tau=TAU, sigma=SIGMA, inner=None, keep=()):
+def run(P, variant, iters, k=1, eps=-1.0, state=None, tau=TAU, sigma=SIGMA, inner=None, keep=(), first_u=None):
     """`iters` outer iterations from `state` (default: P's); returns (phi, rho, alp) as float64 arrays -- with
     keep = (i, ...) a dict of them after those iteration counts instead.
-    inner: a list that receives the dual sub-iteration count of every outer iteration."""
+    inner: a list that receives the dual sub-iteration count of every outer iteration.
+    first_u: a list that receives U1 = (phi1 - phi0) / tau of the first primal update (float64), formed as a test
+    forms it from a context's phi before and after update_primal."""
     primal, dual = oracle_fns(P, rho_alp_iters=k, stats=inner)
     phi, rho, alp = start_state(P, variant, *(state or ()))
     lo = F64 if variant == "f64" else F32
@@ -69,6 +71,8 @@ def run(P, variant, iters, k=1, eps=-1.0, state=None, tau=TAU, sigma=SIGMA, inne
         for i in range(iters):
             u = primal(phi, rho, 70.0, alp, tau, P["dt"], P["dsp"], P["fns"], P["fv"], P["epsl"], x_arr, None)
             phi_n = u.astype(phi.dtype)
+            if i == 0 and first_u is not None:
+                first_u.append((phi_n.astype(F64) - phi.astype(F64)) / tau)
             rho, alp = dual(2 * phi_n - phi, rho, 70.0, alp, sigma, P["dt"], P["dsp"], P["epsl"], P["fns"], x_arr,
                             None, P["ndim"], eps)
             rho, alp = rho.astype(lo), tuple(a.astype(lo) for a in alp)
@@ -78,21 +82,29 @@ def run(P, variant, iters, k=1, eps=-1.0, state=None, tau=TAU, sigma=SIGMA, inne
     return out if keep else out[iters]
 
 
-def errors(P, iters, k=1, eps=-1.0, state=None):
+def errors(P, iters, k=1, eps=-1.0, state=None, f32=True, u1=None):
     """(ref, e_mixed, e32): the float64 run's (phi, rho, alp) and, per quantity ("phi", "rho", "alp0" ..), the relative
     L2 distance of the mixed and of the all-float32 emulation from it after `iters` iterations.  iters a tuple: one
-    run to its largest count, and a dict {count: (ref, e_mixed, e32)}."""
+    run to its largest count, and a dict {count: (ref, e_mixed, e32)}.
+    f32 = False leaves the all-float32 run out (e32 is None then: a check that does not read it saves a third of
+    the time).  u1: a dict that receives the first primal update, "ref" (the float64 run's U1) and "e_mixed" (the
+    mixed emulation's relative L2 distance from it)."""
     counts = tuple(iters) if isinstance(iters, (tuple, list)) else (iters,)
-    runs = {v: run(P, v, max(counts), k, eps, state, keep=counts) for v in ("f64", "mixed", "f32")}
+    variants = ("f64", "mixed") + (("f32",) if f32 else ())
+    first = {v: [] for v in variants}
+    runs = {v: run(P, v, max(counts), k, eps, state, keep=counts, first_u=first[v]) for v in variants}
+    if u1 is not None:
+        u1["ref"] = first["f64"][0]
+        u1["e_mixed"] = rel(first["mixed"][0], first["f64"][0])
     res = {}
     for n in counts:
         ref = runs["f64"][n]
         out = []
-        for variant in ("mixed", "f32"):
+        for variant in variants[1:]:
             r = runs[variant][n]
             e = {"phi": rel(r[0], ref[0]), "rho": rel(r[1], ref[1])}
             for a, (x, y) in enumerate(zip(live(P, r[2]), live(P, ref[2]))):
                 e["alp{}".format(a)] = rel(x, y)
             out.append(e)
-        res[n] = (ref, out[0], out[1])
+        res[n] = (ref, out[0], out[1] if f32 else None)
     return res if isinstance(iters, (tuple, list)) else res[iters]

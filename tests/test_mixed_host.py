@@ -8,6 +8,7 @@ import pytest
 import pdhg_oracle as O
 import _mixed_emul as E
 from _problems import make_problem
+from test_gpu_mixed import MIXED_CASES, MIXED_LARGE, mixed_case_emulation
 
 MIXED = 12
 ENV = ("PDHG_DUAL_MULTI", "PDHG_DUAL_HEAD", "PDHG_DUAL_RX", "PDHG_FUSE_RES", "PDHG_SHORT_T", "PDHG_HALF_NT",
@@ -162,6 +163,23 @@ def test_decomposed_classes_raise_value_error(lib):
             SlabContext(0, 2, 4, 2, 256, 256, 2 / 256, 2 / 256, 0.025, xs, xs, precision=prec)
         with pytest.raises(ValueError):
             XSlabContext(0, 2, 2, 256, 256, 1, 2 / 256, 2 / 256, 0.025, xs, xs, precision=prec)
+
+
+@pytest.mark.parametrize("name", [n for n in MIXED_CASES if "@" not in n and n not in MIXED_LARGE])
+def test_shape_cases_meet_the_caps(name):
+    """The caps of tests/test_gpu_mixed.py::test_mixed_instantiation from the emulation alone, for every default-tier
+    case and both of its runs: 4 e_mixed <= 1e-4 for phi and <= 10 x the floor for rho and each control,
+    4 e_mixed(U1) <= 5e-3 from the seeded state, e32(rho) >= 10 e_mixed(rho) from the reference state -- so a loose
+    emulation fails here, without a device, instead of passing a wrong kernel.  The two cases of millions of points
+    (c3_b2_stride, halfreal_b1: 35 s and 17 s of emulation) are left to the GPU test's own pre-check, which asserts the
+    same conditions through the same function.  Found over these cases: reference state e_mixed(rho) 2.9e-8 - 4.4e-8,
+    e32(rho) 4.6e-5 - 7.1e-5, e_mixed(alp) <= 1.5e-7; seeded e_mixed(phi) <= 1.4e-5, rho <= 2.7e-7, alp <= 7.5e-6,
+    U1 <= 1.2e-4 (ny4096_march at its epsl = 0: phi 1.7e-8, U1 3.4e-6; at epsl = 0.1 it misses the phi cap with
+    2.8e-5, see MIXED_SEEDED_EPSL)."""
+    for seeded in (False, True):
+        P = mixed_case_emulation(name, seeded)[0]   # the caps are asserted inside this helper
+        # powers of two throughout (period = max(nx, ny) 2 / 4096 over a power-of-two extent): exact in binary
+        assert min(P["dx"], P["dy"]) == 2.0 / 4096
 
 
 def test_parity_shape_discriminates():

@@ -10,6 +10,7 @@ import pytest
 
 import pdhg_oracle as O
 from test_gpu_configs import CASES, FP64_CASES, FP64_ENV, ONE_STEP
+from test_gpu_mixed import MIXED_CASES, MIXED_ENV
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(os.path.dirname(HERE), "pdhg-optimal-control_amd", "csrc")
@@ -19,7 +20,7 @@ ENV_USED = ("PDHG_FUSE_RES", "PDHG_XT_BATCH", "PDHG_XT_DMA", "PDHG_XT_DMA_HR", "
             "PDHG_HALF_NT", "PDHG_FS16", "PDHG_FS_WIDE", "PDHG_THOMAS_CHUNK", "PDHG_XT64", "PDHG_XT64_VAR", "PDHG_RES64",
             "PDHG_DUAL64", "PDHG_RES64_NT2048", "PDHG_UPD_T1", "PDHG_TC_SPEC", "PDHG_UPD8192", "PDHG_C4_TO",
             "PDHG_T1_XT", "PDHG_T1_G16", "PDHG_FOURSTEP", "PDHG_FUSE_RES1D", "PDHG_SPEC", "PDHG_DUAL_ONE",
-            "PDHG_DUAL_HEAD", "PDHG_K1_OUTER", "PDHG_DUAL_MULTI", "PDHG_FOLD_FIN")
+            "PDHG_DUAL_HEAD", "PDHG_K1_OUTER", "PDHG_DUAL_MULTI", "PDHG_FOLD_FIN", "PDHG_ROWS_VAR")
 
 
 @pytest.fixture(scope="module")
@@ -76,6 +77,14 @@ def test_config_cases_fp32(lib, monkeypatch, name):
 @pytest.mark.parametrize("name", sorted(FP64_CASES))
 def test_config_cases_fp64(lib, monkeypatch, name):
     _check(lib, monkeypatch, FP64_ENV.get(name.partition("+")[2], {}), _meta(name), FP64_CASES[name], precision=8)
+
+
+@pytest.mark.parametrize("name", sorted(MIXED_CASES))
+def test_config_cases_mixed(lib, monkeypatch, name):
+    """tests/test_gpu_mixed.py::test_mixed_instantiation's table (precision 12), the extended-tier cases included."""
+    egno, nx, ny, T, env, expect = MIXED_CASES[name]
+    assert set(MIXED_ENV) <= set(ENV_USED)
+    _check(lib, monkeypatch, env, (egno, 2, nx, ny, T), expect, precision=12)
 
 
 @pytest.mark.parametrize("name", sorted(ONE_STEP))
