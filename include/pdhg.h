@@ -198,6 +198,46 @@ int pdhg_profile_query(pdhg_ctx* ctx, const char* kernel_class, double* total_ms
  * and everything else at 4 (update 28 N, dual 48 N against 16 N / 44 N in fp32 and 32 N / 88 N in fp64). */
 int pdhg_algorithmic_bytes(pdhg_ctx* ctx, int k, const char* kernel_class, double* bytes);
 
+/* ---------------- closed-loop trajectories from the resident controls ----------------
+ * Replaces compute_traj_1d / extend_bdry_2d / compute_traj_2d (run_example.py:18-155, used at :342-393) for windows
+ * whose alp does not fit a host copy: n_sample paths of dx = f(alp(x, t), x, t) dt + sqrt(2 epsl) dW are marched
+ * through the context's T rows on the device, explicit Euler-Maruyama with the context's dt and epsl.  Step
+ * ind = 0 .. T-1 interpolates row T-1-ind of the current alp set (the reference's alp[:, ::-1], :347: the PDE runs
+ * backward from the terminal cost) and forms the velocity with the f >= 0 / f < 0 split of get_f_vals_1d / _2d.
+ * Positions and the update are float64 in every context precision; alp is read as the context stores it.
+ * Interpolation (method 0 linear, 1 nearest) as the reference's:
+ *   1-D linear   jnp.interp(x, x_arr, alp, period = x_period);
+ *   1-D nearest  argmin |x_arr - x mod P|, first index on ties, no wrap (past the last node's midpoint the last
+ *                node, not node 0); the 1-D grid lies in [0, x_period);
+ *   2-D          extend_bdry_2d evaluated point-wise: periodic axes wrap, a Neumann axis (bc_x = 1) repeats its edge
+ *                value outside the grid, center_x / center_y give the period cell [-P/2, P/2) instead of [0, P);
+ *                bilinear, or the nearer node per axis with ties to the lower one (scipy interpn).
+ * f is evaluated at x mod P on periodic axes and at the raw coordinate on the Neumann axis (:139-145).
+ * Noise (only when the context's epsl > 0): `noise` = standard normals [T][n_sample][ndim] drawn by the caller (the
+ * reference's per-step np.random.normal order), or NULL for the device generator: Philox4x32-10 with
+ *   key = (seed low, seed high 32 bits), counter = (s low, s high, step, axis pair),  s = sample_offset + sample index,
+ *   u1 = (((r0 << 32 | r1) >> 11) + 1) 2^-53,  u2 = ((r2 << 32 | r3) >> 11) 2^-53,
+ *   z[axis 2p] = sqrt(-2 ln u1) cos(2 pi u2),  z[axis 2p+1] = sqrt(-2 ln u1) sin(2 pi u2)   (1-D uses z[0]),
+ * a pure function of (seed, s, step, axis): splitting a run into calls with sample_offset, or the internal staging in
+ * sample chunks, does not change a path.
+ * Arrays are host float64, C order: x_init [n_sample][ndim]; outputs, each optional (NULL: neither allocated nor
+ * copied): x_final [n_sample][ndim], traj_x [T+1][n_sample][ndim] (row 0 = x_init), traj_alp [T][n_sample][n_ctrl]
+ * (the sum of the 2 / 4 interpolated arrays).  Device temporaries are staged in sample chunks of a fixed budget.
+ * x_final of one call is a valid x_init of the next: windows are chained in control time, the context holding the
+ * later PDE rows first.  Single contexts of pdhg_create (precision 4, 8, 12); t-slab, x-slab and multi-device
+ * handles return PDHG_ERR_UNSUPPORTED.  PDHG_ERR_ARG: null opts / x_init, n_sample < 1, unknown method, a period <= 0. */
+typedef struct pdhg_traj_opts {
+  long long n_sample;
+  long long sample_offset;      /* global index of this call's sample 0 in the device noise stream (>= 0) */
+  unsigned long long seed;      /* device noise stream */
+  int method;                   /* 0 linear, 1 nearest */
+  int center_x, center_y;
+  int reserved0;
+  double x_period, y_period;    /* y_period is ignored when ndim == 1 */
+} pdhg_traj_opts;
+int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
+                      double* x_final, double* traj_x, double* traj_alp);
+
 /* ---------------- t-slab decomposition (multi-GPU) ----------------
  * New capability: the reference (JAX, single device, README.md:6) has no distributed path.  A window's
  * T_total unknown time rows are split into contiguous slabs, one context (one GPU) each; a slab context

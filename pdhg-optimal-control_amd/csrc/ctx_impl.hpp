@@ -28,6 +28,7 @@
 #include "kernels_fs_wide.hpp"
 #include "kernels_fs16.hpp"
 #include "kernels_xt_f64.hpp"
+#include "kernels_traj.hpp"
 #include "path_plan.hpp"
 
 using namespace pdhg;
@@ -296,6 +297,8 @@ struct Impl : ImplBase {
 
     // ---- coefficient / symbol tables (host fp64 -> R) ----
     std::vector<R> ax(nx), ay(std::max(ny, 1)), lamx(nxg), d0(nxg);
+    grid_x.assign(pb.xs, pb.xs + nx);   // fp64 copies for trajectories(): the caller's arrays need not outlive create
+    if (is2d) grid_y.assign(pb.ys, pb.ys + ny);
     for (int i = 0; i < nx; ++i) {
       const double x = pb.xs[i];
       ax[i] = (R)(pb.egno == 3 ? x : (x - 1.0) * (x - 1.0) + 0.1);   // set_fns.py:145 / :117-118 / :98
@@ -1714,6 +1717,111 @@ struct Impl : ImplBase {
           HIP_TRY(hipMemcpy(buf.get(), kp.alp[h.cur][a] + off, n * sizeof(R), hipMemcpyDeviceToHost));
           for (size_t i = 0; i < n; ++i) alp[((size_t)a * n + i) * nc + c] = (double)buf[i];
         }
+    }
+    return PDHG_OK;
+  }
+
+  // ---------------- closed-loop trajectories (kernels_traj.hpp; include/pdhg.h pdhg_trajectories) ----------------
+  // Samples are staged in chunks: the device temporaries (positions in / out, the chunk's noise and records) stay
+  // within kTrajBudget however many samples and rows the call has.  A chunk's rows are contiguous runs of the
+  // host arrays [step][n][...], copied row by row.
+  static constexpr size_t kTrajBudget = (size_t)64 << 20;
+  std::vector<double> grid_x, grid_y;   // the grid coordinates in fp64 (kp.ax / kp.ay hold f coefficients in R)
+  double* d_xs64 = nullptr;             // ... on the device, uploaded by the first call
+  double* d_ys64 = nullptr;
+  int trajectories(const pdhg_traj_opts& o, const double* x_init, const double* noise, double* x_final, double* traj_x,
+                   double* traj_alp) {
+    if (slab || xslab)
+      return fail(PDHG_ERR_UNSUPPORTED, "trajectories need the whole window in one context (not a t-slab / x-slab)");
+    const int nd = pb.ndim, nc = n_ctrl(), T = pb.T;
+    const double Px = o.x_period, Py = nd == 2 ? o.y_period : 1.0;
+    // the grids the reference builds (run_example.py:273-287): ascending, within one period
+    for (int i = 1; i < pb.nx; ++i)
+      if (!(grid_x[i] > grid_x[i - 1])) return fail(PDHG_ERR_UNSUPPORTED, "trajectories need an ascending x grid");
+    for (int i = 1; nd == 2 && i < pb.ny; ++i)
+      if (!(grid_y[i] > grid_y[i - 1])) return fail(PDHG_ERR_UNSUPPORTED, "trajectories need an ascending y grid");
+    if (!(grid_x[pb.nx - 1] - grid_x[0] < Px) || (nd == 2 && !(grid_y[pb.ny - 1] - grid_y[0] < Py)))
+      return fail(PDHG_ERR_UNSUPPORTED, "the grid spans a period or more");
+    if (nd == 1 && !(grid_x[0] >= 0.0 && grid_x[pb.nx - 1] < Px))
+      return fail(PDHG_ERR_UNSUPPORTED, "1-D trajectories need the grid in [0, x_period) (jnp.interp period=)");
+    int rc;
+    if (!d_xs64) {
+      if ((rc = alloc(&d_xs64, pb.nx))) return rc;
+      H2D(d_xs64, grid_x.data(), pb.nx * sizeof(double));
+      if (nd == 2) {
+        if ((rc = alloc(&d_ys64, pb.ny))) return rc;
+        H2D(d_ys64, grid_y.data(), pb.ny * sizeof(double));
+      }
+    }
+    const bool noisy = pb.epsl > 0;
+    const size_t n = (size_t)o.n_sample;
+    const size_t w_x = (size_t)nd, w_a = (size_t)nc;   // doubles per sample and row
+    const size_t per = sizeof(double) * (2 * w_x + (noisy && noise ? (size_t)T * w_x : 0) +
+                                         (traj_x ? (size_t)(T + 1) * w_x : 0) + (traj_alp ? (size_t)T * w_a : 0));
+    size_t m = std::max<size_t>(kTrajBudget / per, 256) / 256 * 256;   // whole workgroups per chunk
+    m = std::min(m, n);
+    struct Tmp {   // the chunk buffers: one allocation, freed on every way out
+      double* p = nullptr;
+      ~Tmp() { if (p) hipFree(p); }
+    } tmp;
+    if (hipMalloc((void**)&tmp.p, m * per) != hipSuccess)
+      return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the trajectory chunk failed", m * per);
+    double* d_in = tmp.p;
+    double* d_out = d_in + m * w_x;
+    double* d_next = d_out + m * w_x;
+    double* d_noise = nullptr;
+    double* d_rx = nullptr;
+    double* d_ra = nullptr;
+    if (noisy && noise) d_noise = d_next, d_next += (size_t)T * m * w_x;
+    if (traj_x) d_rx = d_next, d_next += (size_t)(T + 1) * m * w_x;
+    if (traj_alp) d_ra = d_next;
+    TrajP<R> a{};
+    a.nx = pb.nx;
+    a.ny = pb.ny;
+    a.T = T;
+    a.bcx = pb.bc_x;
+    a.method = o.method;
+    a.center_x = o.center_x ? 1 : 0;
+    a.center_y = o.center_y ? 1 : 0;
+    a.noise_mode = noisy ? (noise ? 1 : 2) : 0;
+    a.seed = o.seed;
+    a.Px = Px;
+    a.Py = Py;
+    a.dt = pb.dt;
+    a.sq = std::sqrt(2 * pb.epsl * pb.dt);
+    a.inv_dx = 1.0 / pb.dx;
+    a.inv_dy = nd == 2 ? 1.0 / pb.dy : 0.0;
+    a.xs = d_xs64;
+    a.ys = d_ys64;
+    for (int s = 0; s < 2; ++s)
+      for (int k = 0; k < 4; ++k) a.alp[s][k] = kp.alp[s][k];
+    a.ctrl = kp.ctrl;
+    a.x_in = d_in;
+    a.noise = d_noise;
+    a.x_out = d_out;
+    a.rec_x = d_rx;
+    a.rec_a = d_ra;
+    for (size_t c0 = 0; c0 < n; c0 += m) {
+      const size_t mc = std::min(m, n - c0);
+      HIP_TRY(hipMemcpyAsync(d_in, x_init + c0 * w_x, mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
+      for (int j = 0; d_noise && j < T; ++j)
+        HIP_TRY(hipMemcpyAsync(d_noise + (size_t)j * mc * w_x, noise + ((size_t)j * n + c0) * w_x,
+                               mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
+      a.n = mc;
+      a.s0 = (unsigned long long)o.sample_offset + c0;
+      const dim3 grid((unsigned)((mc + 255) / 256)), block(256);
+      if (nd == 1) rc = with_egno<2>([&](auto E) { return launch(k_traj_1d<R, decltype(E)::value>, grid, block, 0, a); });
+      else rc = with_egno<3>([&](auto E) { return launch(k_traj_2d<R, decltype(E)::value>, grid, block, 0, a); });
+      if (rc) return rc;
+      if (x_final)
+        HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, mc * w_x * sizeof(double), hipMemcpyDeviceToHost, stream));
+      for (int j = 0; d_rx && j <= T; ++j)
+        HIP_TRY(hipMemcpyAsync(traj_x + ((size_t)j * n + c0) * w_x, d_rx + (size_t)j * mc * w_x,
+                               mc * w_x * sizeof(double), hipMemcpyDeviceToHost, stream));
+      for (int j = 0; d_ra && j < T; ++j)
+        HIP_TRY(hipMemcpyAsync(traj_alp + ((size_t)j * n + c0) * w_a, d_ra + (size_t)j * mc * w_a,
+                               mc * w_a * sizeof(double), hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
     }
     return PDHG_OK;
   }

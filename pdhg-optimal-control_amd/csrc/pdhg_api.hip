@@ -336,6 +336,22 @@ int pdhg_algorithmic_bytes(pdhg_ctx* ctx, int k, const char* cls, double* bytes)
   });
 }
 
+/* ---------------- closed-loop trajectories ---------------- */
+int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
+                      double* x_final, double* traj_x, double* traj_alp) {
+  if (ctx && reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
+    return fail(PDHG_ERR_UNSUPPORTED, "trajectories need a single context (pdhg_create), not a multi-device one");
+  if (!opts || !x_init) return fail(PDHG_ERR_ARG, "null opts or x_init");
+  if (opts->n_sample < 1) return fail(PDHG_ERR_ARG, "n_sample must be >= 1");
+  if (opts->sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
+  if (opts->method != 0 && opts->method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", opts->method);
+  return dispatch(ctx, [&](auto& im) {
+    if (!(opts->x_period > 0) || (im.pb.ndim == 2 && !(opts->y_period > 0)))
+      return fail(PDHG_ERR_ARG, "periods must be > 0");
+    return im.trajectories(*opts, x_init, noise, x_final, traj_x, traj_alp);
+  });
+}
+
 /* ---------------- t-slab decomposition ---------------- */
 int pdhg_create_slab(const pdhg_problem* prob, int j0, int T_total, int device, pdhg_ctx** out) {
   if (!prob || !out) return fail(PDHG_ERR_ARG, "null argument");

@@ -25,6 +25,8 @@ EXPORTS = (
     "pdhg_set_state", "pdhg_get_state", "pdhg_get_phi_bar", "pdhg_set_phi_bar", "pdhg_get_rows", "pdhg_init_state",
     "pdhg_update_primal", "pdhg_update_dual", "pdhg_errors", "pdhg_inner_error", "pdhg_iterate", "pdhg_set_stop_rules", "pdhg_synchronize",
     "pdhg_device_bytes", "pdhg_path_info", "pdhg_plan_info", "pdhg_profile_enable", "pdhg_profile_query", "pdhg_algorithmic_bytes",
+    # closed-loop trajectories from the resident controls
+    "pdhg_trajectories",
     # t-slab decomposition (multi-GPU)
     "pdhg_create_slab", "pdhg_set_stream", "pdhg_slab_plane_size", "pdhg_slab_begin", "pdhg_slab_carry_gain",
     "pdhg_slab_residual", "pdhg_slab_forward", "pdhg_slab_fixup", "pdhg_slab_long_modes", "pdhg_slab_fixup_nb", "pdhg_slab_backward", "pdhg_slab_primal_finalize", "pdhg_slab_dual",
@@ -71,6 +73,16 @@ class pdhg_stats(ctypes.Structure):
         ("nan_seen", ctypes.c_int), ("first_nan_iter", ctypes.c_int),
     ]
 
+
+class pdhg_traj_opts(ctypes.Structure):
+    _fields_ = [
+        ("n_sample", ctypes.c_longlong), ("sample_offset", ctypes.c_longlong), ("seed", ctypes.c_ulonglong),
+        ("method", ctypes.c_int), ("center_x", ctypes.c_int), ("center_y", ctypes.c_int), ("reserved0", ctypes.c_int),
+        ("x_period", ctypes.c_double), ("y_period", ctypes.c_double),
+    ]
+
+
+TRAJ_METHODS = {"linear": 0, "nearest": 1}
 
 _lib = None
 
@@ -119,6 +131,7 @@ def load():
         "pdhg_profile_enable": ([P, ctypes.c_int], ctypes.c_int),
         "pdhg_profile_query": ([P, ctypes.c_char_p, dp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "pdhg_algorithmic_bytes": ([P, ctypes.c_int, ctypes.c_char_p, dp], ctypes.c_int),
+        "pdhg_trajectories": ([P, ctypes.POINTER(pdhg_traj_opts), dp, dp, dp, dp, dp], ctypes.c_int),
         "pdhg_create_slab": ([ctypes.POINTER(pdhg_problem), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                               ctypes.POINTER(P)], ctypes.c_int),
         "pdhg_set_stream": ([P, P], ctypes.c_int),

@@ -16,6 +16,41 @@ import numpy as np
 from . import _native as N
 
 
+def traj_arguments(ndim, T, x_init, method, x_period, y_period=None, center=(False, False), noise=None,
+                   record=("x", "alp"), seed=0, sample_offset=0):
+    """Checked arguments of PDHGContext.trajectories, before any native call: (options struct, x_init [n, ndim],
+    noise [T, n, ndim] or None, record_x, record_alp).  Raises ValueError on a shape or value the library would
+    refuse, with the shapes spelled out."""
+    if method not in N.TRAJ_METHODS:
+        raise ValueError("method must be 'linear' or 'nearest', not {!r}".format(method))
+    record = (record,) if isinstance(record, str) else tuple(record or ())
+    if set(record) - {"x", "alp"}:
+        raise ValueError("record takes 'x' and / or 'alp', not {!r}".format(record))
+    x0 = np.ascontiguousarray(x_init, dtype=np.float64)
+    want = "[n_sample]" if ndim == 1 else "[n_sample, 2]"
+    if x0.ndim != ndim or (ndim == 2 and x0.shape[1] != 2) or x0.shape[0] < 1:
+        raise ValueError("x_init must be {} with n_sample >= 1, not {}".format(want, x0.shape))
+    n = x0.shape[0]
+    if ndim == 2 and y_period is None:
+        raise ValueError("y_period is required in 2-D")
+    if not (x_period > 0) or (ndim == 2 and not (y_period > 0)):
+        raise ValueError("periods must be > 0")
+    if len(tuple(center)) != 2:
+        raise ValueError("center is a pair (center_x, center_y)")
+    if noise is not None:
+        noise = np.ascontiguousarray(noise, dtype=np.float64)
+        if noise.shape not in ((T, n, ndim),) + (((T, n),) if ndim == 1 else ()):
+            raise ValueError("noise must be [T, n_sample, ndim] = {}, not {}".format((T, n, ndim), noise.shape))
+        noise = noise.reshape(T, n, ndim)
+    if seed < 0 or seed >= 1 << 64 or sample_offset < 0:
+        raise ValueError("seed must fit 64 unsigned bits and sample_offset be >= 0")
+    o = N.pdhg_traj_opts()
+    o.n_sample, o.sample_offset, o.seed, o.method = n, int(sample_offset), int(seed), N.TRAJ_METHODS[method]
+    o.center_x, o.center_y = int(bool(center[0])), int(bool(center[1]))
+    o.x_period, o.y_period = float(x_period), float(y_period if ndim == 2 else 0.0)
+    return o, x0.reshape(n, ndim), noise, "x" in record, "alp" in record
+
+
 class PDHGContext:
     def __init__(self, egno, ndim, nx, ny, T, dx, dy, dt, xs, ys=None, epsl=0.0, c_on_rho=70.0, bc=None,
                  C=1.0, pow=1.0, Ct=1.0, precision="fp32", rho_alp_iters=1, device=0):
@@ -139,6 +174,26 @@ class PDHGContext:
         g = np.ascontiguousarray(g, dtype=np.float64).reshape(self._space)
         self._version += 1
         N.check(self._lib.pdhg_init_state(self._h, N.dptr(g)))
+
+    # ---- consumers of the controls ----
+    def trajectories(self, x_init, method, x_period, y_period=None, center=(False, False), noise=None, seed=0,
+                     record=("x", "alp"), sample_offset=0):
+        """Closed-loop paths through this window's rows on the device (pdhg_trajectories; run_example.py:18-155):
+        (traj_alp [T, n, n_ctrl], traj_x [T+1, n(, 2)], x_final [n(, 2)]) as compute_traj_1d / _2d, from the alp the
+        device holds -- no host copy of it.  A record left out of `record` is neither allocated nor copied and comes
+        back as None.  noise: standard normals [T, n, ndim] (the reference's per-step draws); None with epsl > 0 uses
+        the device's counter-based generator keyed by `seed`, sample i of this call being stream sample
+        sample_offset + i."""
+        o, x0, noise, rec_x, rec_a = traj_arguments(self.ndim, self.T, x_init, method, x_period, y_period, center,
+                                                    noise, record, seed, sample_offset)
+        n = x0.shape[0]
+        tail = () if self.ndim == 1 else (2,)
+        x_final = np.empty((n,) + tail)
+        traj_x = np.empty((self.T + 1, n) + tail) if rec_x else None
+        traj_alp = np.empty((self.T, n, self.n_ctrl)) if rec_a else None
+        N.check(self._lib.pdhg_trajectories(self._h, ctypes.byref(o), N.dptr(x0), N.dptr(noise), N.dptr(x_final),
+                                            N.dptr(traj_x), N.dptr(traj_alp)))
+        return traj_alp, traj_x, x_final
 
     # ---- updates ----
     def update_primal(self, tau):

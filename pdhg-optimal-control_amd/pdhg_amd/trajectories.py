@@ -140,3 +140,25 @@ def run_trajectories(egno, ndim, alp, fns_dict, nt, x_arr, t_arr, x_period, y_pe
         method = "linear"
     return compute_traj_2d(x0, alp_c, fns_dict.f_fn, nt, x1, x2, t1, x_period, y_period, T, bc, center, epsl,
                            method, rng=rng)
+
+
+def host_noise(rng, T, n, ndim):
+    """The [T, n, ndim] standard normals compute_traj_1d / _2d draw from `rng`: one call per step, of the step's
+    x_curr shape ([n] in 1-D, [n, 2] in 2-D), in step order."""
+    shape = (n,) if ndim == 1 else (n, 2)
+    return np.stack([_normal(rng, shape) for _ in range(T)], axis=0).reshape(T, n, ndim)
+
+
+def run_trajectories_device(ctx, egno, ndim, x_period, y_period, epsl, n, rng=None, seed=0):
+    """run_trajectories on the device (PDHGContext.trajectories): the same samples, method and centring, from the alp
+    resident in `ctx` instead of a host copy.  With an `rng` the noise is drawn on the host in the reference's order,
+    so the result equals run_trajectories' with the same generator; without one (and epsl > 0) the device generator
+    keyed by `seed` is used.  Returns (traj_alp, traj_x) as run_trajectories."""
+    x0 = trajectory_samples(egno, ndim, n, x_period, y_period, epsl)
+    method = "nearest" if egno == 2 else "linear"
+    center = (egno == 3, egno == 3)
+    noise = None
+    if rng is not None and epsl > 0:
+        noise = host_noise(rng, ctx.T, len(x0), ndim)
+    traj_alp, traj_x, _ = ctx.trajectories(x0, method, x_period, y_period if ndim == 2 else None, center, noise, seed)
+    return traj_alp, traj_x
