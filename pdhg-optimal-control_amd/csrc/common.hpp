@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "dual_order.hpp"
+
 namespace pdhg {
 
 // raw bit vectors for the buffer load / store builtins
@@ -108,14 +110,6 @@ __device__ __forceinline__ float lane_from_next(float v, float edge) {
                                                                0x130 /* wave_shl:1 */, 0xF, 0xF, false));
 }
 
-// XCD-aware block index remap: hardware deals consecutive workgroups round-robin
-// over the 8 XCDs; remap so each XCD walks a contiguous range of logical blocks
-// (neighbouring tiles share that XCD's L2).  Speed only, never correctness.
-__device__ __forceinline__ int xcd_remap(int b, int nblocks) {
-  const int per = nblocks >> 3;            // blocks per XCD in the full part
-  const int full = per << 3;
-  if (b >= full) return b;                 // tail keeps identity mapping
-  return (b & 7) * per + (b >> 3);
-}
+// (xcd_remap, the XCD-aware block index remap: dual_order.hpp)
 
 }  // namespace pdhg

@@ -215,6 +215,7 @@ struct Impl : ImplBase {
     if (is2d) {
       p.dbg = tun.dbg;
       p.nbsync = tun.nbsync;
+      p.dual_order = pp.dual_order;
     }
     p.slab = slab ? 1 : 0;
     p.j0 = slab ? slab_j0 : 0;

@@ -49,10 +49,14 @@ __global__ void __launch_bounds__(RX * 64, 2) k_dual_lds_2d(KP<R> p, int jchunk,
   const int nx = p.nx, ny = p.ny;
   const size_t plane = (size_t)nx * ny;
   const int lane = threadIdx.x & 63, r = threadIdx.x >> 6;
-  const int x0 = xcd_remap(blockIdx.x, gridDim.x) * RX;
+  // the logical tile of this workgroup (dual_order.hpp): x tile and y strip, from the linear dispatch index
+  const int gx = gridDim.x, gy = gridDim.y;
+  const DualTile tl = dual_tile(blockIdx.x + gx * blockIdx.y, gx, gy, p.dual_order);
+  const int ys = tl.ys;
+  const int x0 = tl.xt * RX;
   const int x = x0 + r;
   const bool live = x >= p.xl0 && x < p.xl1;   // wave-uniform (x-slab ghost / padding rows: neither stored nor summed)
-  const int y = blockIdx.y * YW + YPL * lane;
+  const int y = ys * YW + YPL * lane;
   const int j0 = jbase + blockIdx.z * jchunk;
   const int j1 = min(jend, j0 + jchunk);
   double s[NS];
@@ -254,8 +258,7 @@ __global__ void __launch_bounds__(RX * 64, 2) k_dual_lds_2d(KP<R> p, int jchunk,
           const bool first = lane == 0;
           R c = first ? -m2y[0] * p.inv_dy : m1y[YPL - 1] * p.inv_dy;
           if (use_eps) c = c + p.epsl * ((first ? f4(rn4, 0) : f4(rn4, YPL - 1)) * p.inv_dy2);
-          const int sy = first ? (blockIdx.y == 0 ? nstrip - 1 : blockIdx.y - 1)
-                               : (blockIdx.y + 1 == nstrip ? 0 : blockIdx.y + 1);
+          const int sy = first ? (ys == 0 ? nstrip - 1 : ys - 1) : (ys + 1 == nstrip ? 0 : ys + 1);
           p.ey[(((size_t)j * nx + x) * nstrip + sy) * 2 + (first ? 1 : 0)] = c;
         }
         // likewise the neighbouring tiles' edge rows (wave-uniform): the last wave feeds row 0 of the next
@@ -298,7 +301,9 @@ __global__ void __launch_bounds__(RX * 64, 2) k_dual_lds_2d(KP<R> p, int jchunk,
                  inner || p.last_slab);
     }
   }
-  block_reduce_store<NS>(s, p.partials, ((zbase + (int)blockIdx.z) * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x);
+  // the partial row the tile has under the x-fastest order, whichever workgroup ran it: the fixed-order fp64
+  // reduction sees the same rows in the same order
+  block_reduce_store<NS>(s, p.partials, ((zbase + (int)blockIdx.z) * gy + ys) * gx + xcd_unmap(tl.xt, gx));
 }
 
 }  // namespace pdhg

@@ -80,6 +80,7 @@ struct PathPlan {
   bool fast_dual = false;         // row-per-thread / LDS-row time-marching dual instead of the per-point kernel
   int dual_rx = 0;                // > 0: k_dual_lds_2d with dual_rx x rows per workgroup (x neighbours through LDS)
   int dual_ypl = 4;               // y per lane of k_dual_lds_2d (fp64: 4 or 2)
+  int dual_order = 0;             // workgroup -> tile order of k_dual_lds_2d (dual_order.hpp: 0 x-fastest, XB > 0 band)
   int dual_one = 0;               // as launched: k_dual_fast_2d<.., ONE> on one-row workgroups (0: marching form)
   bool dual_multi = false;        // rho_alp_iters > 1: the dual loop in chunks of sub-iterations
   bool dual_head = false;         // ... below 2^25 points: sub-iteration 0 alone, the rest in chunks
@@ -357,6 +358,17 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
         pl.gzd = 1;
       }
     }
+    // workgroup -> tile order of k_dual_lds_2d (PDHG_DUAL_ORDER; dual_order.hpp): the band order (XB = 1, each XCD's
+    // workgroups across whole grid rows) for the fused sweep on the 2048^2 and 4096^2 grids, where every freshly
+    // created context ran the dual below the x-fastest order's median (interleaved A/B, 4 contexts each,
+    // profiles/r07_ab_dual_order_*.txt): C3 fp64 61.19 -> 59.76 ms, C3 fp32 31.34 -> 28.14, c3w100 fp64 30.69 -> 29.63,
+    // c3w25 fp64 8.33 -> 7.52, C2 fp64 9.89 -> 8.18, C2 fp32 4.52 -> 4.16 (XB = 2 / 4 within the spread of XB = 1).
+    // ny = 8192 (c4w50: fp64 58.32 -> 57.94, fp32 29.97 -> 29.38 median, but one band context of four above the
+    // median in each) keeps the x-fastest order, as do the sweeps without the fused residual (not measured) and the
+    // t-slab and x-slab contexts, the multi-device ones included (measured on single contexts only)
+    // (reads dual_rx, fuse_res, gxd, gyd)
+    const bool band_dflt = pl.fuse_res && pl.gxd * pl.gyd >= 1024 && (ny == 2048 || ny == 4096);
+    pl.dual_order = (pl.dual_rx && !slab && !xslab) ? tn.dual_order.value_or(band_dflt ? 1 : 0) : 0;
     // C4 (ny = 8192 with half-real x blocks, B = 1): the fused residual's task-order spectrum + a transpose into the
     // blocked layout instead of 16-B chunk stores (fp64 RW = 2 / fp32 RW = 4 tasks: 16-B elements)
     pl.to_c4 = pl.fuse_res && pl.half_real && B == 1 && ny == 8192 && !xslab &&

@@ -64,7 +64,10 @@ struct Tuning {
   // same results; measured (round 4, interleaved A/B at C3): fp32 dual 31.16 -> 31.85 ms, fp64 60.39 -> 60.39 ms,
   // so the barrier is not what bounds the sweep and the default stays the barrier
   bool nbsync = false;
-  int dbg = 0;             // PDHG_DBG: timing experiments only (KP::dbg)
+  // PDHG_DUAL_ORDER: workgroup -> tile order of k_dual_lds_2d (dual_order.hpp).  0: x-fastest (one y strip resident
+  // at a time); 1 / 2 / 4: band order with XB = 1 / 2 / 4 x tiles per band (an XCD's workgroups cover whole grid rows)
+  EnvInt dual_order;
+  int dbg = 0;            // PDHG_DBG: timing experiments only (KP::dbg)
 
   // ---- 1-D ----
   EnvInt fourstep;         // PDHG_FOURSTEP=0: nx = 65536 through the generic global-scratch passes
@@ -117,6 +120,8 @@ struct Tuning {
     t.dual_ypl = env_int("PDHG_DUAL_YPL");
     t.dual_one = env_int("PDHG_DUAL_ONE", t.dual_one);
     t.nbsync = env_flag("PDHG_DUAL_NBSYNC", t.nbsync);
+    if ((t.dual_order = env_int("PDHG_DUAL_ORDER")) && *t.dual_order != 1 && *t.dual_order != 2 && *t.dual_order != 4)
+      t.dual_order = 0;
     t.dbg = env_int("PDHG_DBG", t.dbg);
     t.fourstep = env_int("PDHG_FOURSTEP");
     t.fs_wide = env_flag("PDHG_FS_WIDE", t.fs_wide);
