@@ -79,7 +79,7 @@ typedef struct pdhg_stats {
   double err1;       /* primal error ||phi'-phi||/||phi|| of the last executed iteration     */
   double err2;       /* dual error (utils/utils_pdhg_solver.py:60-68)                         */
   double err_inner;  /* last dual sub-iteration error (update_fns_in_pdhg.py:162-164)        */
-  double rho_min, rho_max; /* not computed (NaN) unless requested; reserved                 */
+  double rho_min, rho_max; /* not computed (NaN); pdhg_report_state gives the rho range     */
   int nan_seen;      /* a NaN appeared in phi' or rho' during this call                        */
   int first_nan_iter; /* iteration of this call (1-based) whose phi' or rho' first held a NaN; 0: none */
 } pdhg_stats;
@@ -237,6 +237,46 @@ typedef struct pdhg_traj_opts {
 } pdhg_traj_opts;
 int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
                       double* x_final, double* traj_x, double* traj_alp);
+
+/* ---------------- solution report: HJ and continuity residual norms of the resident state ----------------
+ * Replaces evaluating compute_HJ_residual_1d / _2d (update_fns_in_pdhg.py:49-70) and compute_cont_residual_1d / _2d
+ * (:72-96) on the returned arrays, for windows that do not fit a host copy.  One read-only device pass over phi (not
+ * phi_bar) and the current rho / alp set.  Point (j, x, y), j = 0 .. T-1, pairs HJ residual row j,
+ *   r = Dt phi - epsl Lap phi - f(alp) . D phi - L(alp)     (<= 0 everywhere and = 0 where rho > 0 at the saddle point),
+ * rho row j, phi row j+1 and continuity residual row j+1 of the reference's [T+1] array, c (= 0 at the saddle point: it
+ * is what the primal step adds to phi; the window's last row carries + c_on_rho / dt).  r and c are formed in the
+ * context's precision with the iteration's own device functions (a mixed context: the phi differences and the time /
+ * epsl terms in double, rounded to float once, as its dual step); the accumulation is fp64 in a fixed order (no
+ * atomics: a call repeats bit for bit).
+ * A point where any of r, c, rho, phi is not finite counts in n_nonfinite and is left out of every sum, mean, maximum
+ * and minimum; means divide by n_points - n_nonfinite; if that is 0 every double is NaN.
+ * Both calls leave the state, phi_bar, the iteration's buffers, its stop bookkeeping and a captured graph untouched.
+ * The first call on a context allocates the report's own table of partial rows (128 bytes per workgroup of the
+ * largest launch: up to a few MiB on the largest grids), which pdhg_device_bytes counts from then on.
+ * Single contexts of pdhg_create (precision 4, 8, 12; ndim 1 and 2); t-slab, x-slab and multi-device handles return
+ * PDHG_ERR_UNSUPPORTED (their halo rows are not resident).  PDHG_ERR_ARG: null ctx / out, a bad row range.
+ * Path key "report_tile" 1/0 (pdhg_path_info / pdhg_plan_info): the 8-row tile kernel that reads every array once
+ * (2-D, nx % 8 == 0, ny % 256 == 0, bc (0,0) or (1,0)); environment PDHG_REPORT_TILE=0 selects the per-point kernel.
+ * "report_wgs": the workgroups the tile kernel aims for (grids with fewer tiles split the window into time chunks;
+ * default 1024, environment PDHG_REPORT_WGS; 0 without the tile kernel). */
+typedef struct pdhg_report {
+  long long n_points;     /* T * nx * ny */
+  long long n_nonfinite;  /* points left out of everything below */
+  long long n_rho_zero;   /* finite points with rho == 0 */
+  long long reserved0;
+  double hj_l1, hj_l2, hj_max;   /* mean |r|, sqrt(mean r^2), max |r| */
+  double hj_pos_max;             /* max of max(r, 0): violation of r <= 0 */
+  double hj_active_max;          /* max |r| over points with rho > 0 (0 when there is none) */
+  double compl_l1;               /* sum rho |r| / sum rho (0 when sum rho == 0) */
+  double cont_l1, cont_l2, cont_max;
+  double rho_min, rho_max, rho_mean;
+  double phi_min, phi_max;       /* over the unknown rows 1..T */
+} pdhg_report;
+int pdhg_report_state(pdhg_ctx* ctx, pdhg_report* out);
+/* Rows [row0, row0 + nrows) (row0 >= 0, nrows >= 1, row0 + nrows <= T) of the two fields, host float64
+ * [nrows][nx][ny]; a null pointer is skipped.  The values pdhg_report_state reduces (the device planes are staged in
+ * row chunks of a fixed budget). */
+int pdhg_report_rows(pdhg_ctx* ctx, int row0, int nrows, double* hj, double* cont);
 
 /* ---------------- t-slab decomposition (multi-GPU) ----------------
  * New capability: the reference (JAX, single device, README.md:6) has no distributed path.  A window's

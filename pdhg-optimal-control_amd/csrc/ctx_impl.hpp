@@ -29,6 +29,7 @@
 #include "kernels_fs16.hpp"
 #include "kernels_xt_f64.hpp"
 #include "kernels_traj.hpp"
+#include "kernels_report.hpp"
 #include "path_plan.hpp"
 
 using namespace pdhg;
@@ -1823,6 +1824,147 @@ struct Impl : ImplBase {
         HIP_TRY(hipMemcpyAsync(traj_alp + ((size_t)j * n + c0) * w_a, d_ra + (size_t)j * mc * w_a,
                                mc * w_a * sizeof(double), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
+    }
+    return PDHG_OK;
+  }
+
+  // ---------------- solution report (kernels_report.hpp; include/pdhg.h pdhg_report_state / _rows) ----------------
+  // Read-only on everything the iteration owns: the kernels take kp by value and write only the report's own partial
+  // table (allocated by the first call) and, for report_rows, staged field planes of at most kReportBudget bytes.
+  static constexpr size_t kReportBudget = (size_t)64 << 20;
+  // y per lane of the tile kernel: 16-B loads of phi (fp64 and mixed: 2 doubles; the mixed kernel spilled 70 VGPRs
+  // at 4 and ran behind the per-point kernel), fp32: 4 floats
+  static constexpr int kRepYpl = sizeof(P) == 8 ? 2 : 4;
+  double* rep_partials = nullptr;   // [rows of the largest launch: report_rows_cap][kNumSums], then the folded row
+  int rep_cap = 0;
+  struct RepGrid {
+    dim3 grid, block;
+    int rows, jchunk;
+  };
+  int report_tiles() const { return (pb.nx / 8) * (pb.ny / (64 * kRepYpl)); }
+  // time chunks the tile kernel starts with for nj rows: enough for report_wgs workgroups where the tiles are few
+  int report_chunks(int nj) const {
+    const int tiles = report_tiles();
+    return std::max(1, std::min(nj, (pp.report_wgs + tiles - 1) / tiles));
+  }
+  // launch shape over nj time rows
+  RepGrid report_grid(int nj) const {
+    RepGrid g{};
+    g.jchunk = nj;
+    if (pb.ndim == 2 && pp.report_tile) {
+      const int gx = pb.nx / 8, gy = pb.ny / (64 * kRepYpl), tiles = gx * gy;
+      int gz = report_chunks(nj);
+      g.jchunk = (nj + gz - 1) / gz;
+      gz = (nj + g.jchunk - 1) / g.jchunk;   // whole chunks, the last one ragged: <= report_chunks(nj)
+      g.grid = dim3(gx, gy, gz);
+      g.block = dim3(512);
+      g.rows = tiles * gz;
+      return g;
+    }
+    const int n = pb.ndim == 2 ? pb.ny : pb.nx;                  // threads along the contiguous axis
+    const long long lines = pb.ndim == 2 ? (long long)nj * pb.nx : nj;
+    const int gx = (n + 255) / 256;
+    const int G = (int)std::max<long long>(1, std::min<long long>(lines, 8192 / gx));
+    g.grid = dim3(gx, G);
+    g.block = dim3(256);
+    g.rows = gx * G;
+    return g;
+  }
+  // Partial rows of the largest launch over any row range of the window.  The tile grid's chunk count after rounding
+  // to whole chunks is not monotone in nj (T = 5 with 4 chunks wanted runs 3 chunks of 2 rows, a 4-row range 4 of 1),
+  // so the bound is the count before rounding at nj = T, which is; the per-point grids grow with nj.
+  int report_rows_cap() const {
+    if (pb.ndim == 2 && pp.report_tile) return report_tiles() * report_chunks(pb.T);
+    return report_grid(pb.T).rows;
+  }
+  int report_ready() {
+    if (slab || xslab)
+      return fail(PDHG_ERR_UNSUPPORTED, "the report needs the whole window in one context (a t-slab's / x-slab's "
+                                        "halo rows are not resident)");
+    if (!rep_partials) {
+      rep_cap = report_rows_cap();
+      if (int rc = alloc(&rep_partials, (size_t)(rep_cap + 1) * kNumSums)) return rc;
+    }
+    return PDHG_OK;
+  }
+  // the pass over time rows [j0, j1): a partial row per workgroup, the field rows into d_hj / d_cont where given
+  int launch_report(int j0, int j1, double* d_hj, double* d_cont, int* rows) {
+    const RepGrid g = report_grid(j1 - j0);
+    if (g.rows > rep_cap) return fail(PDHG_ERR_STATE, "report table of %d rows for a launch of %d", rep_cap, g.rows);
+    *rows = g.rows;
+    const RepP rp{j0, j1, g.jchunk, d_hj, d_cont, rep_partials};
+    if (pb.ndim == 1)
+      return with_egno<2>([&](auto E) { return launch(k_report_1d<R, decltype(E)::value>, g.grid, g.block, 0, kp, rp); });
+    if (pp.report_tile)
+      return with_egno<3>([&](auto E) {
+        return launch(k_report_tile_2d<R, decltype(E)::value, kRepYpl, P>, g.grid, g.block, 0, kp, px, rp);
+      });
+    return with_egno<3>(
+        [&](auto E) { return launch(k_report_2d<R, decltype(E)::value, P>, g.grid, g.block, 0, kp, px, rp); });
+  }
+  int report_state(pdhg_report* out) {
+    int rc, rows = 0;
+    if ((rc = report_ready())) return rc;
+    double* d_out = rep_partials + (size_t)rep_cap * kNumSums;
+    {
+      ProfScope ps(this, "report");
+      if ((rc = launch_report(0, pb.T, nullptr, nullptr, &rows))) return rc;
+      if ((rc = launch(k_report_finalize, dim3(1), dim3(1024), 0, (const double*)rep_partials, rows, d_out))) return rc;
+    }
+    double h[kNumSums];
+    HIP_TRY(hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    pdhg_report r{};
+    r.n_points = (long long)pb.T * pb.nx * pb.ny;
+    r.n_nonfinite = (long long)h[6];
+    r.n_rho_zero = (long long)h[7];
+    const double n = (double)(r.n_points - r.n_nonfinite);
+    if (n > 0) {
+      r.hj_l1 = h[0] / n;
+      r.hj_l2 = std::sqrt(h[1] / n);
+      r.compl_l1 = h[3] == 0.0 ? 0.0 : h[2] / h[3];
+      r.rho_mean = h[3] / n;
+      r.cont_l1 = h[4] / n;
+      r.cont_l2 = std::sqrt(h[5] / n);
+      r.hj_max = h[8];
+      r.hj_pos_max = h[9];
+      r.hj_active_max = h[10];
+      r.cont_max = h[11];
+      r.rho_max = h[12];
+      r.rho_min = -h[13];
+      r.phi_max = h[14];
+      r.phi_min = -h[15];
+    } else {
+      const double nan = std::nan("");
+      r.hj_l1 = r.hj_l2 = r.hj_max = r.hj_pos_max = r.hj_active_max = r.compl_l1 = nan;
+      r.cont_l1 = r.cont_l2 = r.cont_max = r.rho_min = r.rho_max = r.rho_mean = r.phi_min = r.phi_max = nan;
+    }
+    *out = r;
+    return PDHG_OK;
+  }
+  int report_rows(int row0, int nrows, double* hj, double* cont) {
+    int rc, rows = 0;
+    if ((rc = report_ready())) return rc;
+    if (row0 >= pb.T || nrows > pb.T - row0)   // (no row0 + nrows: it may not fit an int)
+      return fail(PDHG_ERR_ARG, "%d rows from row %d outside the residual rows [0, %d)", nrows, row0, pb.T);
+    if (!hj && !cont) return PDHG_OK;
+    const size_t npl = plane(), per = npl * sizeof(double) * ((hj ? 1 : 0) + (cont ? 1 : 0));
+    const int m = (int)std::min<size_t>((size_t)nrows, std::max<size_t>(kReportBudget / per, 1));   // rows per chunk
+    struct Tmp {   // the chunk planes: one allocation, freed on every way out
+      double* p = nullptr;
+      ~Tmp() { if (p) hipFree(p); }
+    } tmp;
+    if (hipMalloc((void**)&tmp.p, (size_t)m * per) != hipSuccess)
+      return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the report rows failed", (size_t)m * per);
+    double* d_hj = hj ? tmp.p : nullptr;
+    double* d_cont = cont ? tmp.p + (hj ? (size_t)m * npl : 0) : nullptr;
+    for (int c0 = 0; c0 < nrows; c0 += m) {
+      const int mc = std::min(m, nrows - c0);
+      if ((rc = launch_report(row0 + c0, row0 + c0 + mc, d_hj, d_cont, &rows))) return rc;
+      const size_t nb = (size_t)mc * npl * sizeof(double);
+      if (hj) HIP_TRY(hipMemcpyAsync(hj + (size_t)c0 * npl, d_hj, nb, hipMemcpyDeviceToHost, stream));
+      if (cont) HIP_TRY(hipMemcpyAsync(cont + (size_t)c0 * npl, d_cont, nb, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));   // the chunk planes are reused
     }
     return PDHG_OK;
   }

@@ -118,6 +118,9 @@ struct PathPlan {
   bool fs16 = false;              // ... as a 16 x 4096 split with a chunk-major spectrum (kernels_fs16.hpp)
   int f16_group = 16;             // rows n1 per load group of k_f16a_fwd_1d
   bool thomas_chunk = false;      // t-solve in chunks of rows (k_thomas_chunk_1d)
+  // solution report (kernels_report.hpp)
+  bool report_tile = false;       // k_report_tile_2d (8-row tiles marching over t) instead of the per-point kernel
+  int report_wgs = 1024;          // ... workgroups it aims for: fewer tiles than that split the window into time chunks
 };
 
 // S = sizeof(real) (4 / 8; a mixed context plans as S = 4 with dc.mixed).  pb is the context's own problem (an
@@ -409,6 +412,11 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     pl.jchunk_1d = (T + pl.gz_1d - 1) / pl.gz_1d;
     pl.gz_1d = (T + pl.jchunk_1d - 1) / pl.jchunk_1d;
   }
+  // the report's tile kernel: whole 8-row x 256-column tiles, y periodic, x periodic or Neumann (its halo rows wrap
+  // or clamp); single contexts (a slab's halo rows are not resident: the report refuses those)
+  pl.report_tile = is2d && nx % 8 == 0 && ny % 256 == 0 && pb.bc_y == 0 && (pb.bc_x == 0 || pb.bc_x == 1) && !slab &&
+                   !xslab && tn.report_tile.value_or(1) != 0;
+  pl.report_wgs = tn.report_wgs;
   pl.g_outer = tn.g_outer;
   pl.head_xrun = tn.head_xrun;
   // rho_alp_iters > 1 on the row-per-thread dual grid, single contexts: the dual loop in chunk passes of
@@ -484,6 +492,8 @@ inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const st
   else if (k == "upd_threads") *value = pl.upd_threads;
   else if (k == "f64_xt") *value = pl.f64_xt ? 1 : 0;   // fp64 nx = 4096 x transform (kernels_xt_f64.hpp)
   else if (k == "t1_xt64") *value = (pl.t1_xt64 && pl.t1_xt) ? 1 : 0;   // fp64 T = 1: carry-free x transform
+  else if (k == "report_tile") *value = pl.report_tile ? 1 : 0;         // pdhg_report_state: the tile kernel
+  else if (k == "report_wgs") *value = pl.report_tile ? pl.report_wgs : 0;   // ... its workgroup target
   else return false;
   return true;
 }

@@ -352,6 +352,21 @@ int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x
   });
 }
 
+/* ---------------- solution report ---------------- */
+int pdhg_report_state(pdhg_ctx* ctx, pdhg_report* out) {
+  if (!ctx || !out) return fail(PDHG_ERR_ARG, "null context or report");
+  if (reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
+    return fail(PDHG_ERR_UNSUPPORTED, "the report needs a single context (pdhg_create), not a multi-device one");
+  return dispatch(ctx, [&](auto& im) { return im.report_state(out); });
+}
+int pdhg_report_rows(pdhg_ctx* ctx, int row0, int nrows, double* hj, double* cont) {
+  if (!ctx) return fail(PDHG_ERR_ARG, "null context");
+  if (row0 < 0 || nrows < 1) return fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0, nrows);
+  if (reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
+    return fail(PDHG_ERR_UNSUPPORTED, "the report needs a single context (pdhg_create), not a multi-device one");
+  return dispatch(ctx, [&](auto& im) { return im.report_rows(row0, nrows, hj, cont); });
+}
+
 /* ---------------- t-slab decomposition ---------------- */
 int pdhg_create_slab(const pdhg_problem* prob, int j0, int T_total, int device, pdhg_ctx** out) {
   if (!prob || !out) return fail(PDHG_ERR_ARG, "null argument");

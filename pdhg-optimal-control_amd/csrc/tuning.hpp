@@ -88,6 +88,12 @@ struct Tuning {
   EnvInt spec;             // PDHG_SPEC=0: iterate() never uses the speculative schedule (A/B, tests)
   bool fin_merge = true;   // PDHG_FIN_MERGE=0: its dual and outer finalizes as two launches (A/B, tests)
 
+  // ---- solution report ----
+  EnvInt report_tile;      // PDHG_REPORT_TILE=0: the per-point report kernel instead of the 8-row tile (A/B, tests)
+  // PDHG_REPORT_WGS: workgroups the tile kernel aims for; grids with fewer tiles split the window into time chunks
+  // (>= 1; 1 = every tile marches the whole window, which is how the tests reach the march on small grids)
+  int report_wgs = 1024;
+
   static Tuning from_env() {
     Tuning t;
     if (const char* e = getenv("PDHG_ALLOC")) t.alloc_mode = !strcmp(e, "contig") ? 1 : !strcmp(e, "none") ? -1 : 0;
@@ -138,6 +144,8 @@ struct Tuning {
     t.dual_head = env_int("PDHG_DUAL_HEAD");
     t.spec = env_int("PDHG_SPEC");
     t.fin_merge = env_flag("PDHG_FIN_MERGE", t.fin_merge);
+    t.report_tile = env_int("PDHG_REPORT_TILE");
+    t.report_wgs = std::max(1, env_int("PDHG_REPORT_WGS", t.report_wgs));
     return t;
   }
 };

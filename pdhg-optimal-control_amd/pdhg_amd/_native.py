@@ -27,6 +27,8 @@ EXPORTS = (
     "pdhg_device_bytes", "pdhg_path_info", "pdhg_plan_info", "pdhg_profile_enable", "pdhg_profile_query", "pdhg_algorithmic_bytes",
     # closed-loop trajectories from the resident controls
     "pdhg_trajectories",
+    # solution report (HJ / continuity residual norms of the resident state)
+    "pdhg_report_state", "pdhg_report_rows",
     # t-slab decomposition (multi-GPU)
     "pdhg_create_slab", "pdhg_set_stream", "pdhg_slab_plane_size", "pdhg_slab_begin", "pdhg_slab_carry_gain",
     "pdhg_slab_residual", "pdhg_slab_forward", "pdhg_slab_fixup", "pdhg_slab_long_modes", "pdhg_slab_fixup_nb", "pdhg_slab_backward", "pdhg_slab_primal_finalize", "pdhg_slab_dual",
@@ -82,6 +84,21 @@ class pdhg_traj_opts(ctypes.Structure):
     ]
 
 
+class pdhg_report(ctypes.Structure):
+    _fields_ = [
+        ("n_points", ctypes.c_longlong), ("n_nonfinite", ctypes.c_longlong), ("n_rho_zero", ctypes.c_longlong),
+        ("reserved0", ctypes.c_longlong),
+        ("hj_l1", ctypes.c_double), ("hj_l2", ctypes.c_double), ("hj_max", ctypes.c_double),
+        ("hj_pos_max", ctypes.c_double), ("hj_active_max", ctypes.c_double), ("compl_l1", ctypes.c_double),
+        ("cont_l1", ctypes.c_double), ("cont_l2", ctypes.c_double), ("cont_max", ctypes.c_double),
+        ("rho_min", ctypes.c_double), ("rho_max", ctypes.c_double), ("rho_mean", ctypes.c_double),
+        ("phi_min", ctypes.c_double), ("phi_max", ctypes.c_double),
+    ]
+
+
+# the fields a report dict carries (PDHGContext.report, pdhg_amd.report.report_from_arrays)
+REPORT_FIELDS = tuple(f for f, _ in pdhg_report._fields_ if f != "reserved0")
+
 TRAJ_METHODS = {"linear": 0, "nearest": 1}
 
 _lib = None
@@ -132,6 +149,8 @@ def load():
         "pdhg_profile_query": ([P, ctypes.c_char_p, dp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "pdhg_algorithmic_bytes": ([P, ctypes.c_int, ctypes.c_char_p, dp], ctypes.c_int),
         "pdhg_trajectories": ([P, ctypes.POINTER(pdhg_traj_opts), dp, dp, dp, dp, dp], ctypes.c_int),
+        "pdhg_report_state": ([P, ctypes.POINTER(pdhg_report)], ctypes.c_int),
+        "pdhg_report_rows": ([P, ctypes.c_int, ctypes.c_int, dp, dp], ctypes.c_int),
         "pdhg_create_slab": ([ctypes.POINTER(pdhg_problem), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                               ctypes.POINTER(P)], ctypes.c_int),
         "pdhg_set_stream": ([P, P], ctypes.c_int),

@@ -195,6 +195,23 @@ class PDHGContext:
                                             N.dptr(traj_x), N.dptr(traj_alp)))
         return traj_alp, traj_x, x_final
 
+    # ---- how good is the state the context holds ----
+    def report(self):
+        """The KKT residual norms of the resident (phi, rho, alp) and the rho / phi ranges (pdhg_report_state): a dict
+        of pdhg_report's fields.  One read-only device pass; the iteration's state and bookkeeping are untouched."""
+        r = N.pdhg_report()
+        N.check(self._lib.pdhg_report_state(self._h, ctypes.byref(r)))
+        return {f: getattr(r, f) for f in N.REPORT_FIELDS}
+
+    def residual_rows(self, row0, nrows, hj=True, cont=True):
+        """Rows [row0, row0 + nrows) of the HJ residual and of the continuity residual (its rows 1.. of the
+        reference's [T+1] array), float64 [nrows, nx(, ny)]: the values report() reduces.  A field passed as False is
+        not computed into a host array and comes back as None."""
+        f = lambda on: np.empty((int(nrows),) + self._space) if on and nrows >= 1 else None  # noqa: E731
+        h, c = f(hj), f(cont)
+        N.check(self._lib.pdhg_report_rows(self._h, int(row0), int(nrows), N.dptr(h), N.dptr(c)))
+        return h, c
+
     # ---- updates ----
     def update_primal(self, tau):
         self._version += 1

@@ -11,7 +11,9 @@ component, their sum; matplotlib, PNG) under plots/<stamp>/eg<egno>_<ndim>d, and
 simulates the controlled trajectories from the solved alp (pdhg_amd.trajectories, run_example.py:342-393)
 and saves them as traj_<prefix>.npz (+ figures).  --tfboard is accepted and ignored (no TensorBoard).
 Extra flags: --precision {fp32,fp64,mixed}, --rho_alp_iters (the reference fixes 10), --out (root dir),
---load_middle / --load_middle_timestamp (resume from middle results, run_example.py:246-248).
+--load_middle / --load_middle_timestamp (resume from middle results, run_example.py:246-248), --report (after
+every window one device pass over its final state: the HJ and continuity residual norms, pdhg_amd.report; the
+window with the largest HJ residual and the last one are printed).
 """
 import argparse
 import os
@@ -63,6 +65,8 @@ def build_parser():
       help="device arithmetic (the reference runs float64)")
     A("--rho_alp_iters", type=int, default=10)
     A("--out", default=".")
+    A("--report", type=int, nargs="?", const=1, default=0,
+      help="print the residual norms of the worst and the last window (--report or --report 1)")
     return ap
 
 
@@ -80,8 +84,8 @@ def make_grid(ndim, egno, nx, ny, nt, x_period, y_period, T):
 def solve_HJ(ndim, n_ctrl, egno, epsl, fns_dict, nx, ny, nt, x_period, y_period, T, x_arr, c_on_rho,
              time_step_per_PDHG, stepsz_param, N_maxiter, print_freq, eps, bc, C=1.0, pow=1.0, Ct=1.0,
              rho_alp_iters=10, precision="fp64", save_middle_dir=None, save_middle_prefix=None, load_middle_dir=None,
-             load_middle_prefix=None, verbose=True):
-    """run_example.py:157-210 with the device-resident update functions."""
+             load_middle_prefix=None, verbose=True, stats=None, report=False):
+    """run_example.py:157-210 with the device-resident update functions.  stats / report: PDHG_multi_step's."""
     dt = T / (nt - 1)
     dx, dy = x_period / nx, y_period / ny
     if ndim == 1:
@@ -97,7 +101,8 @@ def solve_HJ(ndim, n_ctrl, egno, epsl, fns_dict, nx, ny, nt, x_period, y_period,
                                              stepsz_param=stepsz_param, fv=fv, n_ctrl=n_ctrl, N_maxiter=N_maxiter,
                                              print_freq=print_freq, eps=eps, save_middle_dir=save_middle_dir,
                                              save_middle_prefix=save_middle_prefix, load_middle_dir=load_middle_dir,
-                                             load_middle_prefix=load_middle_prefix, verbose=verbose)
+                                             load_middle_prefix=load_middle_prefix, verbose=verbose, stats=stats,
+                                             report=report)
 
 
 def main(argv=None):
@@ -124,6 +129,7 @@ def main(argv=None):
     os.makedirs(save_dir, exist_ok=True)
     fns = set_fns.set_up_example_fns(F.egno, F.ndim, F.numerical_L_ind)
     x_arr, t_arr = make_grid(F.ndim, F.egno, F.nx, F.ny, F.nt, F.x_period, F.y_period, F.T)
+    stats = []
     if F.load:
         results, errs_all = solver.load_solution(save_dir, prefix)
     else:
@@ -134,10 +140,17 @@ def main(argv=None):
                                      save_middle_dir=save_dir if F.save_middle else None,
                                      save_middle_prefix=prefix if F.save_middle else None,
                                      load_middle_dir=save_dir if F.load_middle else None,
-                                     load_middle_prefix=prefix if F.load_middle else None)
+                                     load_middle_prefix=prefix if F.load_middle else None, stats=stats,
+                                     report=bool(F.report))
         if F.save:
             solver.save(save_dir, prefix, (results, errs_all))
     iters, phi = results[-1][0], results[-1][1]
+    reps = [(i, s["report"]) for i, s in enumerate(stats) if "report" in s]
+    if reps:
+        from .report import format_report
+        worst = max(reps, key=lambda r: r[1]["hj_max"] if r[1]["hj_max"] == r[1]["hj_max"] else float("inf"))
+        print("report, worst window (solve {}): {}".format(worst[0], format_report(worst[1])), flush=True)
+        print("report, last window (solve {}): {}".format(reps[-1][0], format_report(reps[-1][1])), flush=True)
     if F.plot:
         plot_results(F, results, x_arr, t_arr, fns, bc, n_ctrl, plot_dir, prefix)
     print("windows: {}  last window iterations: {}  phi shape: {}  saved: {}".format(
