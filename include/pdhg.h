@@ -111,6 +111,10 @@ int pdhg_destroy(pdhg_ctx* ctx);
 int pdhg_set_state(pdhg_ctx* ctx, const double* phi, const double* rho, const double* alp);
 int pdhg_get_state(pdhg_ctx* ctx, double* phi, double* rho, double* alp);
 int pdhg_get_phi_bar(pdhg_ctx* ctx, double* phi_bar);   /* [T+1][nx][ny] */
+/* The spectral work buffer as the last primal update left it: the preconditioner's output (x kernel's inverse
+ * transform rows) in its blocked layout, `count` leading elements converted to double (count <= the buffer's
+ * T * nb * nx * B elements in 2-D, T * nx in 1-D; single contexts).  For tests that pin the x kernels' output itself. */
+int pdhg_get_work(pdhg_ctx* ctx, double* out, long long count);
 /* Rows [row0, row0 + nrows) of the state in the reference layouts (a window of 3.4e9 points per array, C3's and
  * C4's, does not fit a host copy): phi / phi_bar rows of [T+1] -> [nrows][nx][ny], rho rows of [T] -> [nrows][nx][ny],
  * alp -> [n_alp][nrows][nx][ny][n_ctrl] (dead components zero).  Null pointers are skipped; rho / alp need
@@ -171,7 +175,9 @@ int pdhg_device_bytes(pdhg_ctx* ctx, unsigned long long* bytes);
  * contiguous-for-fp32-2-D default), "dual64" 1/0 (fp64 contexts: the row-per-thread time-marching dual
  * k_dual_fast_2d<EGNO, double>, or with nx % 8 == 0 and T >= 3 the LDS-row sweep k_dual_lds_2d<EGNO, 8, .., double>;
  * default on where ny % 256 == 0, environment PDHG_DUAL64=0 selects the generic per-point kernel), "f64_xt" 1/0 (fp64
- * nx = 512 ... 8192: k_precond_xt_f64_2d; PDHG_XT64=0 the generic kernel), "ip_rows" 1/0 (fp64 ny = 8192: row pairs in
+ * nx = 512 ... 8192: k_precond_xt_f64_2d; PDHG_XT64=0 the generic kernel), "xt64_dma" 1/0 (its nx = 4096
+ * column-pair form on single contexts with the forward rows staged by LDS DMA and b' in registers; PDHG_XT64_DMA=0
+ * off; "xt64_bpr" 1/0: b' in registers, PDHG_XT64_BPR), "ip_rows" 1/0 (fp64 ny = 8192: row pairs in
  * one padded line), "upd8192" 1/0 (fp64 ny = 8192 with half-real x blocks: the 2-row fast update), "tc_spec" 1/0
  * (fp64 C3 shape, windows of >= 100 rows: the residual spectrum in task order), "t1_xt64" 1/0 (fp64 one-row windows at a power-of-two nx in
  * 512..4096: the carry-free k_precond_x_t1_2d<..., double>; PDHG_T1_XT=0 off), "graph" 1/0 (pdhg_iterate replays

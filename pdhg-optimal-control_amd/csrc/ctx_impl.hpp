@@ -710,6 +710,15 @@ struct Impl : ImplBase {
             default: return launch(k_precond_xt_f64_2d<2048, 512, false, true>, g, dim3(512), bpr, p, twx);
           }
         }
+        if (pp.xt64_dma) {   // b' in registers, forward rows staged by LDS DMA: static LDS (kernels_xt_f64.hpp, DMA)
+          if (p.rspec) return launch(k_precond_xt_f64_2d<4096, 512, false, true, true, true>, g, dim3(512), 0, p, twx);
+          return launch(k_precond_xt_f64_2d<4096, 512, false, true, false, true>, g, dim3(512), 0, p, twx);
+        }
+        if (pp.xt64_bpr) {   // b' in registers alone (A/B: spills in the forward sweep)
+          const size_t ldsr = (size_t)(Pad<4096>::LINE + TwLds<4096>::SIZE) * sizeof(C);
+          if (p.rspec) return launch(k_precond_xt_f64_2d<4096, 512, false, true, true>, g, dim3(512), ldsr, p, twx);
+          return launch(k_precond_xt_f64_2d<4096, 512, false, true>, g, dim3(512), ldsr, p, twx);
+        }
         const size_t lds = (size_t)(Pad<4096>::LINE + TwLds<4096>::SIZE + 4096) * sizeof(C);
         if (p.rspec)   // task-order residual spectrum in (tc_spec; b' / x rows in `work` as always)
           return launch(k_precond_xt_f64_2d<4096, 512, false, false, true>, g, dim3(512), lds, p, twx);
@@ -1646,6 +1655,16 @@ struct Impl : ImplBase {
     std::vector<R> buf(n);
     HIP_TRY(hipMemcpy(buf.data(), kp.phibar, n * sizeof(R), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; ++i) pbar[i] = (double)buf[i];
+    return PDHG_OK;
+  }
+
+  int get_work(double* out, size_t count) {
+    HIP_TRY(hipStreamSynchronize(stream));
+    const size_t nwork = pb.ndim == 2 ? (size_t)pb.T * kp.nb * pb.nx * kp.B : (size_t)pb.T * pb.nx;
+    if (count > nwork) return fail(PDHG_ERR_ARG, "work buffer holds %zu elements", nwork);
+    std::vector<R> buf(count);
+    HIP_TRY(hipMemcpy(buf.data(), kp.work, count * sizeof(R), hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < count; ++i) out[i] = (double)buf[i];
     return PDHG_OK;
   }
 

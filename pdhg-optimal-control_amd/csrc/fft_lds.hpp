@@ -422,6 +422,35 @@ __device__ __forceinline__ void inplace_passes(C* a, const C* __restrict__ tw, c
   }
 }
 
+// The first pass (LS = 1, radix 16) of one line's padded schedule run out of place: butterfly j reads the 16 elements
+// j + r N/16 of a separate source through read16(j, v) (an unpadded staged line: lanes consecutive in j read
+// consecutive elements, conflict-free) and writes where inplace_pass<.., LS = 1, 16> writes, a[pix(16 j) + r].  The
+// same butterflies on the same values, so the transform that continues with inplace_passes<.., LS = 16> is bitwise
+// lds_fft_inplace's; no barrier inside (the caller orders the source's arrival and a's reuse).
+template <typename C, int N, int NT, class RD>
+__device__ __forceinline__ void first_pass_oop(C* __restrict__ a, RD&& read16) {
+  constexpr int nR = N / 16;
+  static_assert(nR % 16 == 0 && nR <= NT, "padded schedule, one butterfly per thread");
+  // Laid out as inplace_pass is (values read in one block, an opaque statement where its barrier stands, the
+  // butterfly in a block of its own): which product of a constant twiddle multiply the compiler fuses into an fma
+  // depends on the block it sees, and with the read in the butterfly's block it chose differently (last-bit
+  // differences against the in-place pass)
+  const int j = threadIdx.x;
+  C v[16];
+  int base = -1;
+  if (j < nR) {
+    read16(j, v);
+    base = pix(j * 16);
+  }
+  asm volatile("" : "+v"(base)::"memory");
+  if (base >= 0) {
+    dft_any<C, 16>(v);
+    C* d = a + base;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) d[r] = v[r];
+  }
+}
+
 // Forward FFT in place of NL padded line-major lines (element e of line l at a[l*LINE + pix(e)]).
 template <typename C, int N, int NL, int NT, int LINE = Pad<N>::LINE>
 __device__ __forceinline__ void lds_fft_inplace(C* a, const C* __restrict__ tw) {

@@ -1,6 +1,7 @@
 // fp64 x-transform + Thomas in t at nx = 4096 (k_precond_xt_f64_2d) and its row-access helpers.
 #pragma once
 #include "kernels_2d_fast.hpp"
+#include "kernels_xt_dma.hpp"   // lds_addr
 
 namespace pdhg {
 
@@ -15,6 +16,27 @@ __device__ __forceinline__ double2 buf_ld2(__amdgpu_buffer_rsrc_t r, int voff, i
 }
 __device__ __forceinline__ void buf_st2(__amdgpu_buffer_rsrc_t r, int voff, int soff, double2 v) {
   __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), r, voff, soff, 0);
+}
+
+// v[r] = element at a + r * 256 double2 (r < 16) of a DMA-staged line, read in inline asm with its own lgkmcnt wait
+// (as s_read16 of kernels_xt_dma.hpp: the compiler cannot tell that the DMA has landed and would wait vmcnt(0), which
+// also waits for the step's stores, before a read of the staged line it can see)
+__device__ __forceinline__ void s_read16(unsigned a, double2 (&v)[16]) {
+  typedef double d2v __attribute__((ext_vector_type(2)));
+  d2v w[16];
+  asm volatile(
+      "ds_read_b128 %0, %16\n\tds_read_b128 %1, %16 offset:4096\n\tds_read_b128 %2, %16 offset:8192\n\t"
+      "ds_read_b128 %3, %16 offset:12288\n\tds_read_b128 %4, %16 offset:16384\n\tds_read_b128 %5, %16 offset:20480\n\t"
+      "ds_read_b128 %6, %16 offset:24576\n\tds_read_b128 %7, %16 offset:28672\n\tds_read_b128 %8, %16 offset:32768\n\t"
+      "ds_read_b128 %9, %16 offset:36864\n\tds_read_b128 %10, %16 offset:40960\n\tds_read_b128 %11, %16 offset:45056\n\t"
+      "ds_read_b128 %12, %16 offset:49152\n\tds_read_b128 %13, %16 offset:53248\n\t"
+      "ds_read_b128 %14, %16 offset:57344\n\tds_read_b128 %15, %16 offset:61440\n\ts_waitcnt lgkmcnt(0)"
+      : "=&v"(w[0]), "=&v"(w[1]), "=&v"(w[2]), "=&v"(w[3]), "=&v"(w[4]), "=&v"(w[5]), "=&v"(w[6]), "=&v"(w[7]),
+        "=&v"(w[8]), "=&v"(w[9]), "=&v"(w[10]), "=&v"(w[11]), "=&v"(w[12]), "=&v"(w[13]), "=&v"(w[14]), "=&v"(w[15])
+      : "v"(a)
+      : "memory");
+#pragma unroll
+  for (int r = 0; r < 16; ++r) v[r] = make_double2(w[r].x, w[r].y);
 }
 
 __device__ __forceinline__ double eth_of(double dd) {   // e^-th, cosh th = 1 + dd/2 (no cancellation)
@@ -55,32 +77,58 @@ __device__ __forceinline__ double theta_of(double dd) {
 // storing every row, backward sweep from the right carry (carry_y) -- oracle/slab_oracle.py.
 // grid: nb column blocks; block NT; LDS (N + N/16 + TwLds<N> + N (+ 128 HR)) * 16 B.
 // BPR: b' / x of the thread's items in registers instead of the LDS array (nx <= 2048: IT <= 4 items leave the
-// registers for it, and the smaller LDS footprint admits a second workgroup per CU).
+// registers for it, and the smaller LDS footprint admits a second workgroup per CU).  At nx = 4096 (IT = 8, 32
+// registers of b') the 512-thread workgroup runs two waves per SIMD, 256 registers each: with the prefetched row pf
+// also live the forward sweep spills (172 B of scratch, loads and stores inside the row loop), so BPR at nx = 4096
+// is the DMA form's companion (no pf in its forward sweep: no scratch on the converged path) and an A/B switch alone.
 // TC: the forward sweep reads the residual spectrum in task order (p.rspec: per 4-row task, 8 reals per column block
 // b = rows x0..x0+3 at columns 2b, 2b+1): item x = tid + i NT sits at 16 B x (x & 3) of its task's 64-B piece, so
 // the 4 lanes of a task read one contiguous 64-B piece (16 pieces per wave load instead of 1 KiB runs); b' and x go
 // to `work` (blocked) as always.
-template <int N, int NT, bool HR = false, bool BPR = false, bool TC = false>
+// DMA (nx = 4096, 512 threads, with BPR; single contexts): the forward sweep's input rows go HBM -> LDS directly
+// (global_load_lds_dwordx4, per-lane source addresses: the blocked row, or (TC) the 64-B task pieces; destination S
+// linear in kx, the 64 KiB BPR frees) instead of through the pf registers and a staging write of the padded line.
+// The first radix-16 pass (LS = 1) then runs out of place, S -> A (first_pass_oop, fft_lds.hpp: lanes consecutive in
+// j read S[j + 256 r] without conflicts), with the in-place pass's butterflies and output positions, so the transform
+// is bitwise the same.  Row k+1 is issued right after the barrier that follows the first pass of row k (S free) and
+// retired one step later by a counted vmcnt(IT): the step's IT row stores are the only vector-memory operations
+// issued after the DMA, and vmcnt retires in issue order on gfx9.  S is read in inline asm (s_read16), so the
+// compiler adds no vmcnt(0) of its own; the barriers are lgkmcnt-only (lds_sync), so the DMA spans them.  LDS is
+// static then (S, A and the seeds as separate objects: the compiler knows the DMA writes only S): 145 KiB as before.
+// The backward sweep is the BPR form (its b' rows are first used element-wise, in registers).
+template <int N, int NT, bool HR = false, bool BPR = false, bool TC = false, bool DMA = false>
 __global__ void __launch_bounds__(NT) k_precond_xt_f64_2d(KP<double> p, const double2* __restrict__ twx) {
   using C = double2;
   constexpr int IT = N / NT;
   constexpr int LINE = Pad<N>::LINE;
   constexpr int M = 2 * N;   // reals per block row: B = 2 columns of N, or (HR) one column of 2N
   static_assert(N % NT == 0 && N <= 4096 && IT <= 32, "one padded complex line and its twiddle seeds in LDS");
+  static_assert(!DMA || (BPR && !HR && N == 4096 && NT == 512), "DMA staging: the nx = 4096 column-pair form");
   if (p.ctrl->done) return;
   extern __shared__ __align__(16) unsigned char smem_raw[];
-  C* A = reinterpret_cast<C*>(smem_raw);
-  C* twl = A + LINE;
+  C *A, *twl, *S = nullptr;
+  if constexpr (DMA) {
+    __shared__ __align__(16) C A_s[LINE];
+    __shared__ __align__(16) C S_s[N];   // the staged input row, element kx at S[kx]
+    __shared__ __align__(16) C twl_s[TwLds<N>::SIZE];
+    A = A_s;
+    S = S_s;
+    twl = twl_s;
+  } else {
+    A = reinterpret_cast<C*>(smem_raw);
+    twl = A + LINE;
+  }
   C* bp = twl + TwLds<N>::SIZE;   // b' / x per item (BPR: unused, none allocated)
   C* rsw = bp + (BPR ? 0 : N);    // HR: W_{2N}^j and W_{2N}^{64 j}, j < 64
   static_assert(!(BPR && HR), "half-real blocks keep b' in LDS");
-  static_assert(!TC || (!HR && !BPR && NT % 4 == 0), "task-order input: column pairs, 4-row tasks");
+  static_assert(!TC || (!HR && NT % 4 == 0), "task-order input: column pairs, 4-row tasks");
   fill_twlds<C, N>(twl, twx, HR ? 2 : 1);   // HR: twx holds W_{2N}
   if constexpr (HR) {
     static_assert(N == 4096, "split-twiddle tables sized for 2N = 8192");
     for (int i = threadIdx.x; i < 128; i += blockDim.x) rsw[i] = twx[i < 64 ? i : 64 * (i - 64)];
   }
-  const int T = p.T, tid = threadIdx.x;
+  const int T = p.T;
+  int tid = threadIdx.x;
   // t-slab carry exchange: blocks [b0, b0 + gridDim.x).  TC: XCD-aware order, the gridDim/8 workgroups of one XCD
   // take consecutive column blocks, so the two blocks sharing each 128-B line of the task-order input (64 B each)
   // read it through one L2 (round robin put them on different XCDs: every line fetched twice)
@@ -176,15 +224,42 @@ __global__ void __launch_bounds__(NT) k_precond_xt_f64_2d(KP<double> p, const do
     //   last (Neumann) row of the window: x_{T-1} = (rhs/ae + b'_{T-2}) / (dd + h_{T-2})   [converged: dd + h = (1 - g)/g]
     // A t-slab indexes the pivots by the GLOBAL row j0 + k; only the window's last slab has the Neumann row, and
     // a slab stores every row (the backward sweep is a separate launch after the carry fix-up).
-    ldrow_in(0);
+    // DMA: input row kk HBM -> S, one 1-KiB wave instruction per item (item i of the wave's lanes at S[i NT + 64 wave ..])
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    auto issue_row = [&](auto kk) {   // (generic: instantiated by the DMA form only)
+      const char* src = TC ? reinterpret_cast<const char*>(p.rspec + (size_t)kk * kstride + (size_t)8 * b) +
+                                 (32 * ny_t * (tid >> 2) + 16 * (tid & 3))
+                           : reinterpret_cast<const char*>(wb + (size_t)kk * kstride) + voff;
+#pragma unroll
+      for (int i = 0; i < IT; ++i)
+        __builtin_amdgcn_global_load_lds(
+            reinterpret_cast<const u32x4_t*>(src + (TC ? (size_t)8 * ny_t * NT * i : (size_t)ioff(i))),
+            (__attribute__((address_space(3))) void*)(S + i * NT + wave * 64), 16, 0, 0);
+    };
+    if constexpr (DMA) {
+      issue_row(0);
+      __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+      lds_sync();
+    } else {
+      ldrow_in(0);
+    }
     for (int k = 0; k < T; ++k) {
       const int kg = j0 + k;
       const bool nrow = k == T - 1 && p.last_slab;   // the window's Neumann row
+      if constexpr (DMA) {
+        // row k has landed in S (every wave's counted wait, then the barrier that ended the last step)
+        if (!(p.dbg & 8192))   // PDHG_DBG 8192: first pass skipped (timing experiments only, results wrong)
+          first_pass_oop<C, N, NT>(A, [&](int j, C(&v)[16]) { s_read16(lds_addr(S + j), v); });
+        lds_sync();            // S read by every wave: free for the next row; the first pass's A complete
+        if (k + 1 < T) issue_row(k + 1);
+        inplace_passes<C, N, 1, NT, 16, true>(A, nullptr, twl);
+      } else {
 #pragma unroll
-      for (int i = 0; i < IT; ++i) A[pix(kx_of(i))] = pf[i];
-      if (k + 1 < T) ldrow_in(k + 1);
-      lds_sync();
-      lds_fft_inplace_tl<C, N, 1, NT>(A, twl);
+        for (int i = 0; i < IT; ++i) A[pix(kx_of(i))] = pf[i];
+        if (k + 1 < T) ldrow_in(k + 1);
+        lds_sync();
+        lds_fft_inplace_tl<C, N, 1, NT>(A, twl);
+      }
 #pragma unroll
       for (int i = 0; i < IT; ++i)   // items whose pivots have converged switch to g = e^-th (dd -> e^-th) on
         if (kg == max(kf[i], j0) && !nrow)   // the first converged row of this sweep (a slab may start past kf)
@@ -208,13 +283,30 @@ __global__ void __launch_bounds__(NT) k_precond_xt_f64_2d(KP<double> p, const do
             bn = make_double2(r0 * g0, r1 * g1);
             c2[i] = make_double2(s0 * g0, s1 * g1);
           }
-          buf_st2(dst, voff, ioff(i), bn);
+          if constexpr (!DMA) buf_st2(dst, voff, ioff(i), bn);
         } else {
           if (fast) bn = make_double2(r0 * c1[i].x / (1.0 - c1[i].x), r1 * c1[i].y / (1.0 - c1[i].y));
           else bn = make_double2(r0 / (c1[i].x + c2[i].x), r1 / (c1[i].y + c2[i].y));
-          if (slab) buf_st2(dst, voff, ioff(i), bn);   // re-read after the carry fix-up
+          if constexpr (!DMA) if (slab) buf_st2(dst, voff, ioff(i), bn);   // re-read after the carry fix-up
         }
         bp_st(i, bn);
+      }
+      if constexpr (DMA) {
+        // The row's stores from the register copy, in one straight run with the wait that counts them.  Row k+1's
+        // DMA is older than this step's IT stores (k + 1 < T: not the Neumann row, every lane stores its IT items):
+        // at most IT operations outstanding means it has landed.  The last step drains.
+        static_assert(IT == 8, "the counted wait below is vmcnt(8)");
+        if (k + 1 < T) {
+#pragma unroll
+          for (int i = 0; i < IT; ++i) buf_st2(dst, voff, ioff(i), bpr[i]);
+          __builtin_amdgcn_s_waitcnt(0x0F78);   // vmcnt(8) (expcnt, lgkmcnt: no wait)
+        } else {
+          if (!nrow || slab) {
+#pragma unroll
+            for (int i = 0; i < IT; ++i) buf_st2(dst, voff, ioff(i), bpr[i]);
+          }
+          __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0)
+        }
       }
       lds_sync();
     }
@@ -241,6 +333,9 @@ __global__ void __launch_bounds__(NT) k_precond_xt_f64_2d(KP<double> p, const do
   if (ks >= 0) ldrow(ks);
   for (int k = T - 1; k >= 0; --k) {
     const int kg = j0 + k;
+    // b' in registers with IT = 8 fills the 256 registers a wave has at two waves per SIMD: the thread index is made
+    // opaque per row, so the LDS addresses derived from it are recomputed here instead of held across the transform
+    if constexpr (BPR && IT == 8) asm volatile("" : "+v"(tid));
 #pragma unroll
     for (int i = 0; i < IT; ++i)   // items leaving the converged regime: E_{k+2} from theta
       if (kg + 1 == kf[i] && k < ks)

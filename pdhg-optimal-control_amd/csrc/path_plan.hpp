@@ -111,6 +111,8 @@ struct PathPlan {
   bool t1_g16 = false;            // as launched: ... with the later passes' twiddle seeds from global memory
   bool f64_xt = false;            // fp64: in-place line + register carries (k_precond_xt_f64_2d)
   int xt64_var = 0;               // nx = 2048 shape of it (threads, b' in registers or LDS)
+  bool xt64_bpr = false;          // nx = 4096 form of it with b' / x in registers (8 items per thread)
+  bool xt64_dma = false;          // ... and the forward sweep's rows staged by LDS DMA (needs xt64_bpr's 64 KiB)
   // 1-D
   bool glb_line = false;          // line FFTs over global scratch (nx beyond LDS)
   bool fourstep = false;          // nx = 65536: four-step DHT
@@ -183,6 +185,17 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     pl.f64_xt = S == 8 && pb.bc_x == 0 &&
                 (((nxg == 4096 || nxg == 2048) && B == 2) || (nxg == 8192 && pl.half_real) || f64_small) && xt64_on;
     pl.xt64_var = tn.xt64_var;
+    // nx = 4096 column pairs on single contexts (t-slab phases, x-slabs and the half-real blocks keep the LDS b'
+    // line): b' / x in registers, and in the 64 KiB that frees the forward rows staged by LDS DMA, the first
+    // radix-16 pass out of place (PDHG_XT64_DMA; PDHG_XT64_BPR=1 with PDHG_XT64_DMA=0: the register form alone,
+    // A/B -- the DMA form cannot run without it, its staging line is the LDS b' line's space)
+    // (reads f64_xt, half_real, B)
+    {
+      const bool ok = pl.f64_xt && nxg == 4096 && B == 2 && !pl.half_real && !slab && !xslab;
+      const bool dma = ok && tn.xt64_dma.value_or(1) != 0;
+      pl.xt64_bpr = ok && tn.xt64_bpr.value_or(dma ? 1 : 0) != 0;
+      pl.xt64_dma = dma && pl.xt64_bpr;
+    }
     // fp64 one-row windows at a power-of-two nx: the carry-free transform needs only the padded lines
     pl.t1_xt64 = S == 8 && T == 1 && pb.bc_x == 0 && !pl.half_real && !slab && pl.plx.pow2 &&
                  nxg >= 512 && nxg <= 4096 && nxg * (B / 2) == (nxg == 4096 ? 4096 : 2048);
@@ -491,6 +504,8 @@ inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const st
   else if (k == "res_threads") *value = pl.res_threads;
   else if (k == "upd_threads") *value = pl.upd_threads;
   else if (k == "f64_xt") *value = pl.f64_xt ? 1 : 0;   // fp64 nx = 4096 x transform (kernels_xt_f64.hpp)
+  else if (k == "xt64_dma") *value = pl.xt64_dma ? 1 : 0;   // ... nx = 4096: forward rows by LDS DMA, b' in registers
+  else if (k == "xt64_bpr") *value = pl.xt64_bpr ? 1 : 0;   // ... nx = 4096: b' / x in registers
   else if (k == "t1_xt64") *value = (pl.t1_xt64 && pl.t1_xt) ? 1 : 0;   // fp64 T = 1: carry-free x transform
   else if (k == "report_tile") *value = pl.report_tile ? 1 : 0;         // pdhg_report_state: the tile kernel
   else if (k == "report_wgs") *value = pl.report_tile ? pl.report_wgs : 0;   // ... its workgroup target

@@ -220,6 +220,10 @@ int pdhg_get_phi_bar(pdhg_ctx* ctx, double* phi_bar) {
   if (!phi_bar) return fail(PDHG_ERR_ARG, "null phi_bar");
   return dispatch(ctx, [&](auto& im) { return im.get_phi_bar(phi_bar); });
 }
+int pdhg_get_work(pdhg_ctx* ctx, double* out, long long count) {
+  if (!out) return fail(PDHG_ERR_ARG, "null out");
+  return dispatch(ctx, [&](auto& im) { return im.get_work(out, count < 0 ? 0 : (size_t)count); });
+}
 int pdhg_set_phi_bar(pdhg_ctx* ctx, const double* phi_bar) {
   if (!phi_bar) return fail(PDHG_ERR_ARG, "null phi_bar");
   return dispatch(ctx, [&](auto& im) { return im.set_phi_bar(phi_bar); });

@@ -28,6 +28,8 @@ struct Tuning {
   // ---- 2-D x transform ----
   EnvInt xt64;             // PDHG_XT64=0: fp64 generic runtime-radix x kernel instead of k_precond_xt_f64_2d (A/B)
   int xt64_var = 0;        // PDHG_XT64_VAR: nx = 2048 shapes of it (1: 256 threads, b' in LDS; 2: 256; 3: 1024; A/B)
+  EnvInt xt64_dma;         // PDHG_XT64_DMA=0: its nx = 4096 form without LDS-DMA staged forward rows (default on)
+  EnvInt xt64_bpr;         // PDHG_XT64_BPR: ... b' / x in registers (default: with the DMA form, which needs it; A/B)
   bool t1_xt = true;       // PDHG_T1_XT=0: T = 1 windows without the carry-free x transform (k_precond_x_t1_2d)
   bool t1_g16 = true;      // PDHG_T1_G16=0: its fp64 form with every twiddle seed in LDS (A/B)
   int short_t_xt = 16;     // PDHG_SHORT_T_XT: windows below this take the single-role x kernel (0: never)
@@ -99,6 +101,8 @@ struct Tuning {
     if (const char* e = getenv("PDHG_ALLOC")) t.alloc_mode = !strcmp(e, "contig") ? 1 : !strcmp(e, "none") ? -1 : 0;
     t.xt64 = env_int("PDHG_XT64");
     t.xt64_var = env_int("PDHG_XT64_VAR", t.xt64_var);
+    t.xt64_dma = env_int("PDHG_XT64_DMA");
+    t.xt64_bpr = env_int("PDHG_XT64_BPR");
     t.t1_xt = env_flag("PDHG_T1_XT", t.t1_xt);
     t.t1_g16 = env_flag("PDHG_T1_G16", t.t1_g16);
     t.short_t_xt = env_int("PDHG_SHORT_T_XT", t.short_t_xt);

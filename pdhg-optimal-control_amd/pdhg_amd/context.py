@@ -165,6 +165,13 @@ class PDHGContext:
         N.check(self._lib.pdhg_get_phi_bar(self._h, N.dptr(pb)))
         return pb
 
+    def get_work(self, count):
+        """The first `count` elements of the spectral work buffer (after update_primal: the preconditioner's output,
+        blocked layout [T][nb][nx][B])."""
+        out = np.empty(int(count))
+        N.check(self._lib.pdhg_get_work(self._h, N.dptr(out), int(count)))
+        return out
+
     def set_phi_bar(self, phi_bar):
         self._version += 1
         pb = np.ascontiguousarray(phi_bar, dtype=np.float64).reshape((self.T + 1,) + self._space)
