@@ -3,6 +3,7 @@
 // the environment overrides of tuning.hpp.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <memory>
@@ -142,7 +143,9 @@ int validate_problem(const pdhg_problem& p) {
     return fail(PDHG_ERR_UNSUPPORTED, "bc (%d,%d): H1_precond_2d supports (0,0) and (1,0) only "
                                       "(utils_precond.py:157-163)", p.bc_x, p.bc_y);
   if (p.ndim == 1 && p.Ct < 0) return fail(PDHG_ERR_ARG, "Ct must be >= 0");
-  if (p.C < 0) return fail(PDHG_ERR_ARG, "C must be >= 0");
+  // C u - Lap u (utils_precond.py:151: "C = 0 and 1 are both fine"); a negative or non-finite C makes
+  // dd = (C - lam) dt^2 negative or NaN at the low modes and the pivots' square root NaN without an error
+  if (!(p.C >= 0) || !std::isfinite(p.C)) return fail(PDHG_ERR_ARG, "C must be finite and >= 0 (got %g)", p.C);
   return PDHG_OK;
 }
 

@@ -6,10 +6,11 @@ import pdhg_oracle as O
 SEED = 20250117   # SURVEY.md §8(d) seeded state
 
 
-def make_problem(egno, ndim, nx, ny, T, epsl, seeded=True, seed=SEED, period=2.0):
+def make_problem(egno, ndim, nx, ny, T, epsl, seeded=True, seed=SEED, period=2.0, dt=None):
     ny = ny if ndim == 2 else 1
     x_arr = O.make_grid(ndim, nx, ny, egno, period, period)
-    dt = 1.0 / max(T, 40)                 # C0 time step (T_hor = 1, nt = 41) unless the window is longer
+    if dt is None:
+        dt = 1.0 / max(T, 40)             # C0 time step (T_hor = 1, nt = 41) unless the window is longer
     dx, dy = period / nx, period / ny
     bc = O.default_bc(egno, ndim)
     fns = O.set_up_example_fns(egno, ndim, 0)

@@ -58,7 +58,10 @@ def _prob(lib, **kw):
 
 
 @pytest.mark.parametrize("field,value", [("egno", 4), ("ndim", 3), ("T", 0), ("precision", 2), ("nx", 2),
-                                         ("rho_alp_iters", 0), ("dt", 0.0)])
+                                         ("rho_alp_iters", 0), ("dt", 0.0), ("Ct", -1.0),
+                                         # H1 solve parameter: "positive number", 0 allowed (utils_precond.py:151)
+                                         ("C", -1.0), ("C", -1e-300), ("C", float("nan")), ("C", float("inf")),
+                                         ("C", float("-inf"))])
 def test_create_rejects_bad_arguments(lib, field, value):
     L = lib.load()
     p, xs = _prob(lib, **{field: value})

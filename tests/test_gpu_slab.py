@@ -34,10 +34,10 @@ CASES = [
 ]
 
 
-def _slabs(P, nranks, k):
+def _slabs(P, nranks, k, **kw):
     from pdhg_amd.slab import SlabContext
     return [SlabContext(r, nranks, P["T"], P["egno"], P["nx"], P["ny"], P["dx"], P["dy"], P["dt"], P["xs"], P["ys"],
-                        epsl=P["epsl"], rho_alp_iters=k) for r in range(nranks)]
+                        epsl=P["epsl"], rho_alp_iters=k, **kw) for r in range(nranks)]
 
 
 MODES = [(True, "neighbour", "overlap-nb"), (False, "neighbour", "serial-nb"), (True, "allgather", "overlap-ag")]
@@ -179,3 +179,55 @@ def test_slabs_fused_residual(native, egno, nx, ny, T, nr, monkeypatch):
     for s in slabs:
         s.close()
     ref.close()
+
+
+@pytest.mark.parametrize("C,dt", [(0.0, 1 / 400), (100.0, 1 / 40)], ids=["C0_dt1/400", "C100_dt1/40"])
+def test_slabs_fused_solve_parameter(native, parity_log, monkeypatch, C, dt):
+    """The fp32 slab phases at nx = 4096 (8-row slabs: the LDS-DMA x transform; fused residual) with the solve
+    parameter away from C = 1: at C = 0 the zero mode's carry gain stops decaying, so the long-range set cannot shrink
+    (K(C = 0) >= K(C = 1), both logged).  Against the fused single context with the same (C, dt), the bounds of
+    test_slabs_fused_residual."""
+    import torch
+    from pdhg_amd.context import PDHGContext
+    from pdhg_amd.slab import LocalComm, SlabRunner, join_state, slab_bounds, split_state
+    monkeypatch.setenv("PDHG_FUSE_RES", "1")
+    monkeypatch.setenv("PDHG_SHORT_T", "0")
+    egno, nx, ny, T, nr = 2, 4096, 256, 16, 2
+    P = make_problem(egno, 2, nx, ny, T, 0.0, dt=dt)
+    tau, sigma, n = 0.1 / 1.5, 0.1 * 1.5, 6
+    ref = PDHGContext(egno, 2, nx, ny, T, P["dx"], P["dy"], dt, P["xs"], P["ys"], precision="fp32", C=C)
+    slabs = []
+    try:
+        assert ref.path_info("fused_residual") == 1 and ref.path_info("fast_xt") == 4
+        ref.set_state(P["phi"], P["rho"], P["alp"])
+        st_ref = ref.iterate(n, tau, sigma, -1.0, 1)
+        phi_r, rho_r, alp_r = ref.get_state()
+        Ks = {}
+        for Ck in (1.0, C):   # the long-range mode count at C = 1 and at this C
+            slabs = _slabs(P, nr, 1, C=Ck)
+            runner = SlabRunner(slabs, LocalComm(nr))
+            Ks[Ck] = runner.n_long
+            if Ck != C:
+                for s in slabs:
+                    s.close()
+        for s in slabs:
+            assert s.path_info("fused_residual") == 1 and s.path_info("fast_xt") == 4
+        for s, part in zip(slabs, split_state(P["phi"], P["rho"], P["alp"], slab_bounds(T, nr))):
+            s.set_state(*part)
+        st = runner.iterate(n, tau, sigma, -1.0, 1)
+        torch.cuda.synchronize()
+        phi_s, rho_s, alp_s = join_state([s.get_state() for s in slabs])
+    finally:
+        for s in slabs:
+            s.close()
+        ref.close()
+    m = {"phi": rel(phi_s, phi_r), "rho": rel(rho_s, rho_r), "alp": rel(np.stack(alp_s), np.stack(alp_r)),
+         "err1": abs(st["err1"] - st_ref["err1"]) / st_ref["err1"]}
+    b = {"phi": 2e-5, "rho": 2e-4, "alp": 2e-4, "err1": 1e-3}
+    parity_log("test_slabs_fused_solve_parameter", "e2_4096x256_T16_P2_C{:g}_dt{:g}".format(C, dt), m, b, K=Ks[C],
+               K_C1=Ks[1.0])
+    assert st["iters"] == st_ref["iters_run"] == n
+    assert all(0 <= K <= nx * ny for K in Ks.values())
+    if C == 0.0:
+        assert Ks[C] >= Ks[1.0], Ks
+    assert all(m[q] < b[q] for q in m), (m, b)

@@ -45,8 +45,9 @@ def _ids(cases):
     return ["e{}_{}x{}_T{}_P{}_k{}".format(*c[:6]) for c in cases]
 
 
-def _run_pair(P, nr, k, n, path=None, egno=None, alp=None):
-    """alp (default: below C3's 4096^2 plane): compare the controls too; at 4096^2 their reference-layout host copies
+def _run_pair(P, nr, k, n, path=None, egno=None, alp=None, **kw):
+    """kw: further context arguments of both sides (the solve parameter C).  The slab runner's long-range mode count
+    comes back as st["n_long"].  alp (default: below C3's 4096^2 plane): compare the controls too; at 4096^2 their reference-layout host copies
     (dead components included) cost more than the whole run, and err2 (compared) sums their changes anyway."""
     if alp is None:
         alp = P["nx"] * P["ny"] < 4096 * 4096
@@ -56,7 +57,7 @@ def _run_pair(P, nr, k, n, path=None, egno=None, alp=None):
     egno = P["egno"]
     T = P["T"]
     ref = PDHGContext(egno, 2, P["nx"], P["ny"], T, P["dx"], P["dy"], P["dt"], P["xs"], P["ys"], epsl=P["epsl"],
-                      precision="fp64", rho_alp_iters=k)
+                      precision="fp64", rho_alp_iters=k, **kw)
     try:
         ref.set_state(P["phi"], P["rho"], P["alp"])
         st_ref = ref.iterate(n, TAU, SIGMA, -1.0, k)
@@ -64,7 +65,7 @@ def _run_pair(P, nr, k, n, path=None, egno=None, alp=None):
     finally:
         ref.close()
     slabs = [SlabContext(r, nr, T, egno, P["nx"], P["ny"], P["dx"], P["dy"], P["dt"], P["xs"], P["ys"],
-                         epsl=P["epsl"], rho_alp_iters=k, precision="fp64") for r in range(nr)]
+                         epsl=P["epsl"], rho_alp_iters=k, precision="fp64", **kw) for r in range(nr)]
     try:
         for s in slabs:
             for key, v in (path or {}).items():
@@ -74,6 +75,7 @@ def _run_pair(P, nr, k, n, path=None, egno=None, alp=None):
         runner = SlabRunner(slabs, LocalComm(nr))
         assert runner.b[0]["DS"].dtype == torch.float64   # exchange planes in the slabs' precision
         st = runner.iterate(n, TAU, SIGMA, -1.0, k)
+        st["n_long"] = runner.n_long
         torch.cuda.synchronize()
         parts = [s.get_state(alp=alp) for s in slabs]
         got = join_state(parts) if alp else join_state([(a, b, ()) for a, b, _ in parts])[:2] + (None,)
@@ -251,3 +253,85 @@ def test_fp64_slabs_c4_task_order(native, parity_log, monkeypatch):
          "err2": abs(st["err2"] - st_ref["err2"]) / st_ref["err2"]}
     parity_log("test_fp64_slabs_c4_task_order", "e2_8192x8192_T4_P2_eps0.1", m, {k: TOL for k in m})
     assert all(v <= TOL for v in m.values()), m
+
+
+# The solve parameter through the slab phases: at C = 0 the zero mode's dd = 0, the slab carry gains G stop decaying
+# (the set pdhg_slab_long_modes returns grows) and h_entry(0, j0) runs through its theta -> 0 limit.
+SOLVE_PARAMS = [(0.0, 1 / 400), (100.0, 1 / 40)]
+SOLVE_CASES = [
+    (2, 4096, 256, 11, 3, {"f64_xt": 1}),   # 4 + 4 + 3 rows
+    (2, 4096, 256, 50, 2, {"f64_xt": 1}),   # 25-row slabs
+    (1, 512, 256, 3, 3, {"f64_xt": 1}),     # one-row slabs
+    (3, 512, 256, 9, 3, {"f64_xt": 0}),     # the generic kernel's DCT slab phases
+]
+SOLVE_IDS = ["e{}_{}x{}_T{}_P{}".format(*c[:5]) for c in SOLVE_CASES]
+
+
+def _n_long(P, nr, **kw):
+    from pdhg_amd.slab import LocalComm, SlabContext, SlabRunner
+    slabs = [SlabContext(r, nr, P["T"], P["egno"], P["nx"], P["ny"], P["dx"], P["dy"], P["dt"], P["xs"], P["ys"],
+                         epsl=P["epsl"], precision="fp64", **kw) for r in range(nr)]
+    try:
+        return SlabRunner(slabs, LocalComm(nr)).n_long
+    finally:
+        for s in slabs:
+            s.close()
+
+
+@pytest.mark.parametrize("C,dt", SOLVE_PARAMS, ids=["C0_dt1/400", "C100_dt1/40"])
+@pytest.mark.parametrize("egno,nx,ny,T,nr,path", SOLVE_CASES, ids=SOLVE_IDS)
+def test_fp64_slabs_solve_parameter(native, parity_log, egno, nx, ny, T, nr, path, C, dt):
+    """fp64 t-slabs at (C, dt) = (0, 1/400) and (100, 1/40) against the single fp64 context with the same parameters:
+    6 iterations from the seeded state at TOL, as test_fp64_slabs_match_single_context.  The long-range mode count K
+    at this C and at C = 1 (same dt) is logged; at C = 0 the zero mode cannot become shorter-ranged: K(0) >= K(1)."""
+    P = make_problem(egno, 2, nx, ny, T, 0.0, dt=dt)
+    st, st_ref, got, want = _run_pair(P, nr, 1, 6, path, C=C)
+    assert st["iters"] == st_ref["iters_run"] == 6
+    assert all(np.isfinite(a).all() for a in (got[0], got[1], want[0], want[1]))
+    K, K1 = st.pop("n_long"), _n_long(P, nr, C=1.0)
+    m = _metrics(st, st_ref, got, want)
+    case = "e{}_{}x{}_T{}_P{}_C{:g}_dt{:g}".format(egno, nx, ny, T, nr, C, dt)
+    parity_log("test_fp64_slabs_solve_parameter", case, m, {key: TOL for key in m}, K=K, K_C1=K1)
+    assert 0 <= K <= nx * ny and 0 <= K1 <= nx * ny
+    if C == 0.0:
+        assert K >= K1, (K, K1)
+    assert all(v <= TOL for v in m.values()), m
+
+
+@pytest.mark.parametrize("C,dt", SOLVE_PARAMS, ids=["C0_dt1/400", "C100_dt1/40"])
+@pytest.mark.parametrize("egno,nx,ny,T,nr,path", [
+    c if c[1] < 4096 else pytest.param(*c, marks=pytest.mark.extended) for c in SOLVE_CASES], ids=SOLVE_IDS)
+def test_fp64_slabs_solve_parameter_vs_oracle(native, parity_log, egno, nx, ny, T, nr, path, C, dt):
+    """One iteration of the same slabs against the fp64 oracle at (C, dt): the fixed 1e-9 of
+    test_fp64_slab_eps_one_step_vs_oracle.  (The oracle step of the nx = 4096 windows takes 7 s at T = 11 and 33 s at
+    T = 50, most of it the controls' host arrays: extended tier; their slabs are held to the single context above.)"""
+    import torch
+    from pdhg_amd.slab import LocalComm, SlabContext, SlabRunner, join_state, slab_bounds, split_state
+    P = make_problem(egno, 2, nx, ny, T, 0.0, dt=dt)
+    slabs = [SlabContext(r, nr, T, egno, nx, ny, P["dx"], P["dy"], dt, P["xs"], P["ys"], precision="fp64", C=C)
+             for r in range(nr)]
+    try:
+        for s in slabs:
+            for key, v in path.items():
+                assert s.path_info(key) == v, (key, s.path_info(key), v)
+        for s, part in zip(slabs, split_state(P["phi"], P["rho"], P["alp"], slab_bounds(T, nr))):
+            s.set_state(*part)
+        SlabRunner(slabs, LocalComm(nr)).iterate(1, TAU, SIGMA, -1.0, 1)
+        torch.cuda.synchronize()
+        got = join_state([s.get_state() for s in slabs])
+    finally:
+        for s in slabs:
+            s.close()
+    primal, dual = oracle_fns(P, C=C)
+    phi_n = primal(P["phi"], P["rho"], 70.0, P["alp"], TAU, dt, P["dsp"], P["fns"], P["fv"], 0.0, P["x_arr"], None)
+    rho_n, alp_n = dual(2 * phi_n - P["phi"], P["rho"], 70.0, P["alp"], SIGMA, dt, P["dsp"], 0.0, P["fns"],
+                        P["x_arr"], None, 2, -1.0)
+    m = {"phi": rel(got[0], phi_n), "rho": rel(got[1], rho_n),
+         "U": rel((got[0] - P["phi"]) / TAU, (phi_n - P["phi"]) / TAU)}
+    for a in range(4):
+        if np.linalg.norm(alp_n[a]) > 0:
+            m["alp%d" % a] = rel(got[2][a], alp_n[a])
+    b = {key: 1e-9 for key in m}
+    parity_log("test_fp64_slabs_solve_parameter_vs_oracle",
+               "e{}_{}x{}_T{}_P{}_C{:g}_dt{:g}".format(egno, nx, ny, T, nr, C, dt), m, b)
+    assert all(m[key] <= b[key] for key in m), (m, b)

@@ -36,10 +36,10 @@ CASES = [
 ]
 
 
-def _xslabs(P, nranks, k, precision="fp32"):
+def _xslabs(P, nranks, k, precision="fp32", **kw):
     from pdhg_amd.xslab import XSlabContext
     return [XSlabContext(r, nranks, P["egno"], P["nx"], P["ny"], P["T"], P["dx"], P["dy"], P["dt"], P["xs"], P["ys"],
-                         epsl=P["epsl"], rho_alp_iters=k, precision=precision) for r in range(nranks)]
+                         epsl=P["epsl"], rho_alp_iters=k, precision=precision, **kw) for r in range(nranks)]
 
 
 def _state(slabs):
@@ -323,3 +323,59 @@ def test_xslab_distcomm_gloo_rehearsal(native, prec):
     for rank, it, it_ref, e_phi, e_err1 in res:
         assert it == it_ref == 6, res
         assert e_phi < tol_phi and e_err1 < tol_err, res
+
+
+@pytest.mark.parametrize("prec,nx,ny,T,nr,path", [("fp32", 512, 256, 8, 2, {"fast_xt": 1}),
+                                                  ("fp64", 512, 2048, 3, 2, {"f64_xt": 1})], ids=["fp32", "fp64"])
+def test_xslabs_undamped_zero_mode(native, parity_log, prec, nx, ny, T, nr, path):
+    """x-slabs with the solve parameter C = 0 (dt = 1/40; the x transform's theta -> 0 branch of the zero mode on the
+    transposed whole lines): 6 iterations against the single context with C = 0 at the bounds of
+    test_xslabs_match_single_context / test_fp64_xslabs_match_single_context, and the first of them against the fp64
+    oracle with C = 0 (fp64: 1e-9 as test_fp64_xslab_vs_oracle; fp32: phi 1e-5 as test_xslab_vs_oracle)."""
+    import torch
+    from pdhg_amd.context import PDHGContext
+    from pdhg_amd.xslab import LocalComm, XSlabRunner
+    C, dt = 0.0, 1 / 40
+    P = make_problem(2, 2, nx, ny, T, 0.0, dt=dt)
+    tau, sigma, n = 0.1 / 1.5, 0.1 * 1.5, 6
+    primal, dual = oracle_fns(P, C=C)
+    phi_o = primal(P["phi"], P["rho"], 70.0, P["alp"], tau, dt, P["dsp"], P["fns"], P["fv"], 0.0, P["x_arr"], None)
+    rho_o, _ = dual(2 * phi_o - P["phi"], P["rho"], 70.0, P["alp"], sigma, dt, P["dsp"], 0.0, P["fns"], P["x_arr"],
+                    None, 2, -1.0)
+    ref = PDHGContext(2, 2, nx, ny, T, P["dx"], P["dy"], dt, P["xs"], P["ys"], precision=prec, C=C)
+    try:
+        ref.set_state(P["phi"], P["rho"], P["alp"])
+        st_ref = ref.iterate(n, tau, sigma, -1.0, 1)
+        phi_r, rho_r, alp_r = ref.get_state()
+    finally:
+        ref.close()
+    slabs = _xslabs(P, nr, 1, prec, C=C)
+    try:
+        for s in slabs:
+            for key, v in path.items():
+                assert s.path_info(key) == v, (key, s.path_info(key), v)
+            s.set_global_state(P["phi"], P["rho"], P["alp"])
+        runner = XSlabRunner(slabs, LocalComm(nr))
+        runner.iterate(1, tau, sigma, -1.0, 1)
+        torch.cuda.synchronize()
+        phi_1, rho_1, _ = _state(slabs)
+        for s in slabs:
+            s.set_global_state(P["phi"], P["rho"], P["alp"])
+        st = runner.iterate(n, tau, sigma, -1.0, 1)
+        torch.cuda.synchronize()
+        phi_s, rho_s, alp_s = _state(slabs)
+    finally:
+        for s in slabs:
+            s.close()
+    assert not st_ref["nan_seen"] and not st["nan_seen"] and st["iters"] == st_ref["iters_run"] == n
+    m = {"phi": rel(phi_s, phi_r), "rho": rel(rho_s, rho_r), "alp": rel(np.stack(alp_s), np.stack(alp_r)),
+         "err1": abs(st["err1"] - st_ref["err1"]) / st_ref["err1"],
+         "err2": abs(st["err2"] - st_ref["err2"]) / st_ref["err2"],
+         "phi_vs_oracle": rel(phi_1, phi_o), "rho_vs_oracle": rel(rho_1, rho_o)}
+    if prec == "fp64":
+        b = {key: (1e-9 if key.endswith("oracle") else 1e-11) for key in m}
+    else:
+        b = {"phi": 2e-5, "rho": 2e-4, "alp": 2e-4, "err1": 1e-4, "err2": 1e-4, "phi_vs_oracle": 1e-5,
+             "rho_vs_oracle": 1e-5}
+    parity_log("test_xslabs_undamped_zero_mode", "e2_{}x{}_T{}_P{}_{}".format(nx, ny, T, nr, prec), m, b)
+    assert all(m[q] < b[q] for q in m), (m, b)
