@@ -27,6 +27,11 @@
  * either one process per GPU with a t-slab / x-slab context each and the caller's
  * communicator (pdhg_create_slab, pdhg_create_xslab; pdhg_amd/slab.py over RCCL), or
  * one host thread over a device list (pdhg_create_multi).  See DESIGN.md §7.
+ * The two post-processing passes -- the solution report and the closed-loop trajectories -- run on single contexts
+ * (pdhg_report_state / pdhg_report_rows / pdhg_trajectories), on multi-device contexts (pdhg_multi_report_state /
+ * pdhg_multi_report_rows / pdhg_multi_trajectories) and slab by slab on t-slab contexts (pdhg_slab_report /
+ * pdhg_slab_report_rows / pdhg_slab_trajectories, chained by the caller: pdhg_amd/slab.py SlabRunner.report);
+ * x-slab contexts have neither.
  */
 #ifndef PDHG_MI355X_H
 #define PDHG_MI355X_H
@@ -79,7 +84,7 @@ typedef struct pdhg_stats {
   double err1;       /* primal error ||phi'-phi||/||phi|| of the last executed iteration     */
   double err2;       /* dual error (utils/utils_pdhg_solver.py:60-68)                         */
   double err_inner;  /* last dual sub-iteration error (update_fns_in_pdhg.py:162-164)        */
-  double rho_min, rho_max; /* not computed (NaN); pdhg_report_state gives the rho range     */
+  double rho_min, rho_max; /* not computed (NaN); pdhg_report_state / pdhg_multi_report_state give the rho range */
   int nan_seen;      /* a NaN appeared in phi' or rho' during this call                        */
   int first_nan_iter; /* iteration of this call (1-based) whose phi' or rho' first held a NaN; 0: none */
 } pdhg_stats;
@@ -231,7 +236,8 @@ int pdhg_algorithmic_bytes(pdhg_ctx* ctx, int k, const char* kernel_class, doubl
  * (the sum of the 2 / 4 interpolated arrays).  Device temporaries are staged in sample chunks of a fixed budget.
  * x_final of one call is a valid x_init of the next: windows are chained in control time, the context holding the
  * later PDE rows first.  Single contexts of pdhg_create (precision 4, 8, 12); t-slab, x-slab and multi-device
- * handles return PDHG_ERR_UNSUPPORTED.  PDHG_ERR_ARG: null opts / x_init, n_sample < 1, unknown method, a period <= 0. */
+ * handles return PDHG_ERR_UNSUPPORTED from this entry point (a multi-device context: pdhg_multi_trajectories; a
+ * t-slab: pdhg_slab_trajectories).  PDHG_ERR_ARG: null opts / x_init, n_sample < 1, unknown method, a period <= 0. */
 typedef struct pdhg_traj_opts {
   long long n_sample;
   long long sample_offset;      /* global index of this call's sample 0 in the device noise stream (>= 0) */
@@ -260,7 +266,8 @@ int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x
  * The first call on a context allocates the report's own table of partial rows (128 bytes per workgroup of the
  * largest launch: up to a few MiB on the largest grids), which pdhg_device_bytes counts from then on.
  * Single contexts of pdhg_create (precision 4, 8, 12; ndim 1 and 2); t-slab, x-slab and multi-device handles return
- * PDHG_ERR_UNSUPPORTED (their halo rows are not resident).  PDHG_ERR_ARG: null ctx / out, a bad row range.
+ * PDHG_ERR_UNSUPPORTED from these two entry points (their halo rows are not resident; a multi-device context:
+ * pdhg_multi_report_state / _rows, a t-slab: pdhg_slab_report / _rows).  PDHG_ERR_ARG: null ctx / out, a bad row range.
  * Path key "report_tile" 1/0 (pdhg_path_info / pdhg_plan_info): the 8-row tile kernel that reads every array once
  * (2-D, nx % 8 == 0, ny % 256 == 0, bc (0,0) or (1,0)); environment PDHG_REPORT_TILE=0 selects the per-point kernel.
  * "report_wgs": the workgroups the tile kernel aims for (grids with fewer tiles split the window into time chunks;
@@ -336,7 +343,8 @@ int pdhg_slab_dual_finalize(pdhg_ctx* ctx, double eps, int sub, const double* su
 int pdhg_slab_outer(pdhg_ctx* ctx, int rho_alp_iters, double* sums);
 int pdhg_slab_outer_finalize(pdhg_ctx* ctx, double eps, int rho_alp_iters, const double* sums);
 int pdhg_slab_plane_out(pdhg_ctx* ctx, int which, void* dst); /* 0 rho row 0, 1 phi_bar row T, 2 [D, S1],
-                                                                 3 [D, S1] of the long-range modes */
+                                                                 3 [D, S1] of the long-range modes,
+                                                                 4 phi row T (the next slab's report halo) */
 int pdhg_slab_plane_in(pdhg_ctx* ctx, int which, const void* src); /* 0 rho halo, 1 phi_bar row 0 */
 int pdhg_slab_status(pdhg_ctx* ctx, pdhg_stats* st);
 /* Partitioned carry exchange (pdhg_amd.slab default): the column blocks are split into nparts parts so the
@@ -352,6 +360,42 @@ int pdhg_slab_fixup_nb_part(pdhg_ctx* ctx, const void* D_left, const void* S1_ri
                             const void* all_GS, int rank, int nranks, int part, int nparts);
 int pdhg_slab_backward_part(pdhg_ctx* ctx, double tau, int part, int nparts);
 int pdhg_slab_update(pdhg_ctx* ctx, double tau, double* sums);            /* inverse y + update + sums */
+/* The solution report and the trajectories slab by slab (what pdhg_multi_report_state / _report_rows / _trajectories
+ * chain; pdhg_report_state, pdhg_report_rows and pdhg_trajectories themselves stay refused on a t-slab).  Every
+ * pointer below is a device pointer used on the context's stream; nothing is staged through the host and nothing
+ * synchronises (the first report call allocates the partial table and, on a slab with j0 > 0, one plane in phi's type
+ * for the phi halo, both counted by pdhg_device_bytes; the first trajectory call uploads the grid coordinates).  All
+ * three leave the state, phi_bar and the loop control untouched.
+ * Report: residual row j of a slab owning global rows [j0, j0 + T) reads two planes the slab does not hold fresh:
+ *   rho row T   = the next slab's rho row 0.  The slab's halo is stale after the last dual sweep: before the pass the
+ *                 caller delivers it again, next slab plane_out(0) -> [move] -> plane_in(0) (not on the last slab, whose
+ *                 row T is the window's zero row and which alone adds c_on_rho / dt);
+ *   phi row 0   = the previous slab's phi row T when j0 > 0 (the iteration maintains phi_bar row 0 only):
+ *                 previous slab plane_out(4) -> [move] -> phi_prev_rowT here (null on the first slab); it is copied
+ *                 into the report's own plane, never into the slab's phi.
+ * pdhg_slab_report: one pass over the slab's rows folded to one row of 16 doubles in `sums`:
+ *   [0] sum |r| [1] sum r^2 [2] sum rho |r| [3] sum rho [4] sum |c| [5] sum c^2 [6] non-finite points [7] points
+ *   rho == 0; [8] max |r| [9] max max(r, 0) [10] max |r| where rho > 0 [11] max |c| [12] max rho [13] max -rho
+ *   [14] max phi [15] max -phi.
+ * The window's report folds the slabs' rows IN SLAB ORDER (columns 0-7 added, 8-15 maximised; an all-reduce has no
+ * fixed order) and is then pdhg_report's arithmetic with n_points = T_total nx ny.
+ * pdhg_slab_report_rows: rows [row0_local, row0_local + nrows) of the slab's two fields into device planes
+ * [nrows][nx][ny] of doubles (a null plane is skipped).  The values are bit for bit the single context's rows on the
+ * same state (same device functions, same operand order).
+ * pdhg_slab_trajectories: the slab's T steps of a rollout over T_total rows.  Control time runs against PDE time, so
+ * the LAST slab marches first (step0 = 0) and a slab's step0 = the rows of the slabs after it; its local step ind
+ * reads its row T-1-ind and is global step step0 + ind: the Philox step word, the row of d_noise
+ * ([T_total][n][2], or null: device generator when epsl > 0) and the row of the records d_rec_x [T_total+1][n][2]
+ * (rows step0+1 .. step0+T written; row 0 too when step0 = 0) and d_rec_a [T_total][n][n_ctrl] (rows step0 ..
+ * step0+T-1), each optional.  n = the samples of this launch (opts->n_sample is not read), opts->sample_offset = the
+ * global index of its sample 0; d_x_in / d_x_out [n][2] (they may be the same buffer).  d_x_out of one slab is d_x_in
+ * of the slab before it.  PDHG_ERR_ARG: null opts / positions, n < 1, step0 outside [0, rows after this slab], a bad
+ * method or period. */
+int pdhg_slab_report(pdhg_ctx* ctx, const void* phi_prev_rowT, double* sums);
+int pdhg_slab_report_rows(pdhg_ctx* ctx, const void* phi_prev_rowT, int row0_local, int nrows, double* d_hj,
+                          double* d_cont);
+int pdhg_slab_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, int step0, long long n, const double* d_x_in,
+                           const double* d_noise, double* d_x_out, double* d_rec_x, double* d_rec_a);
 
 /* ---------------- x-slab decomposition (multi-GPU for T = 1 marching windows) -----------
  * New capability (the reference has no distributed path).  The reference's default marches windows of
@@ -410,6 +454,23 @@ int pdhg_multi_iterate(pdhg_multi* m, int n_iters, double tau, double sigma, dou
 int pdhg_multi_set_stop_rules(pdhg_multi* m, int stop_on_converge, int stop_on_nan);
 int pdhg_multi_synchronize(pdhg_multi* m);
 int pdhg_multi_info(pdhg_multi* m, const char* key, int* value);   /* + "parts", "device:<i>" */
+/* The solution report and the trajectories of the whole window (contracts, layouts and values of pdhg_report_state /
+ * pdhg_report_rows / pdhg_trajectories with T = p->T; host arrays).  All three drain the slab streams, leave the
+ * states, phi_bar, the loop control and the long-range classification untouched and return with every stream idle.
+ * report_state: rho row 0 of slab r+1 is delivered to slab r's halo and phi row T of slab r-1 to slab r's report,
+ * device to device, then every slab runs pdhg_slab_report on its own device and stream; the ndev rows are folded on
+ * the host in slab order (a repeated call returns the same bits).  Counts and extrema equal the single context's on the
+ * same state; the six sum-derived fields differ from it by the re-association of fp64 sums only.
+ * report_rows: GLOBAL rows [row0, row0 + nrows) (a range may span slabs), staged per slab in row chunks of the single
+ * context's budget; bit for bit the single context's rows.
+ * trajectories: per sample chunk (the single context's budget rule with T = p->T) the positions enter the last slab at
+ * step 0 and are handed slab to slab device to device; each slab uploads its steps' noise rows and returns its steps'
+ * record rows.  Bit for bit the single context's paths on the same controls.
+ * Run so far with every slab on one device only (devices = {0, 0, ...}), like the rest of this context. */
+int pdhg_multi_report_state(pdhg_multi* m, pdhg_report* out);
+int pdhg_multi_report_rows(pdhg_multi* m, int row0, int nrows, double* hj, double* cont);
+int pdhg_multi_trajectories(pdhg_multi* m, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
+                            double* x_final, double* traj_x, double* traj_alp);
 /* Per-phase timing of the choreography (events on slab 0's main stream, cross-slab waits included) while
  * enabled; phases "residual", "forward", "backward", "allreduce", "dual", "outer", "step". */
 int pdhg_multi_profile(pdhg_multi* m, int enable);

@@ -52,6 +52,36 @@ struct ProfEntry {
   size_t used = 0;
 };
 
+// pdhg_report from one folded row of kNumSums report sums (kernels_report.hpp) over n_points points
+inline pdhg_report report_from_sums(const double* h, long long n_points) {
+  pdhg_report r{};
+  r.n_points = n_points;
+  r.n_nonfinite = (long long)h[6];
+  r.n_rho_zero = (long long)h[7];
+  const double n = (double)(r.n_points - r.n_nonfinite);
+  if (n > 0) {
+    r.hj_l1 = h[0] / n;
+    r.hj_l2 = std::sqrt(h[1] / n);
+    r.compl_l1 = h[3] == 0.0 ? 0.0 : h[2] / h[3];
+    r.rho_mean = h[3] / n;
+    r.cont_l1 = h[4] / n;
+    r.cont_l2 = std::sqrt(h[5] / n);
+    r.hj_max = h[8];
+    r.hj_pos_max = h[9];
+    r.hj_active_max = h[10];
+    r.cont_max = h[11];
+    r.rho_max = h[12];
+    r.rho_min = -h[13];
+    r.phi_max = h[14];
+    r.phi_min = -h[15];
+  } else {
+    const double nan = std::nan("");
+    r.hj_l1 = r.hj_l2 = r.hj_max = r.hj_pos_max = r.hj_active_max = r.compl_l1 = nan;
+    r.cont_l1 = r.cont_l2 = r.cont_max = r.rho_min = r.rho_max = r.rho_mean = r.phi_min = r.phi_max = nan;
+  }
+  return r;
+}
+
 struct ImplBase {
   int device = 0;   // every entry point selects it before touching the context (dispatch)
   virtual ~ImplBase() {}
@@ -1452,7 +1482,7 @@ struct Impl : ImplBase {
                   stop_nan, kp.ctrl, 0);
   }
   // planes out: 0 rho row 0 (current set), 1 phi_bar row T, 2 [D, S1] (2 spectral planes),
-  // 3 [D, S1] of the long-range modes (2 x long_K)
+  // 3 [D, S1] of the long-range modes (2 x long_K), 4 phi row T (the next slab's report halo)
   int slab_plane_out(int which, void* dst) {
     const size_t npl = plane();
     switch (which) {
@@ -1465,6 +1495,7 @@ struct Impl : ImplBase {
           return launch(k_slab_gather_long<R>, dim3((unsigned)((long_K + 255) / 256)), dim3(256), 0, dsbuf, Mspec,
                         long_idx, long_K, (R*)dst);
         break;
+      case 4: HIP_TRY(hipMemcpyAsync(dst, kp.phi + (size_t)pb.T * npl, npl * sizeof(R), hipMemcpyDeviceToDevice, stream)); break;
       default: return fail(PDHG_ERR_ARG, "unknown plane %d", which);
     }
     return PDHG_OK;
@@ -1750,11 +1781,9 @@ struct Impl : ImplBase {
   std::vector<double> grid_x, grid_y;   // the grid coordinates in fp64 (kp.ax / kp.ay hold f coefficients in R)
   double* d_xs64 = nullptr;             // ... on the device, uploaded by the first call
   double* d_ys64 = nullptr;
-  int trajectories(const pdhg_traj_opts& o, const double* x_init, const double* noise, double* x_final, double* traj_x,
-                   double* traj_alp) {
-    if (slab || xslab)
-      return fail(PDHG_ERR_UNSUPPORTED, "trajectories need the whole window in one context (not a t-slab / x-slab)");
-    const int nd = pb.ndim, nc = n_ctrl(), T = pb.T;
+  // the grid checks of a rollout and the fp64 grid on the device (uploaded by the first call)
+  int traj_ready(const pdhg_traj_opts& o) {
+    const int nd = pb.ndim;
     const double Px = o.x_period, Py = nd == 2 ? o.y_period : 1.0;
     // the grids the reference builds (run_example.py:273-287): ascending, within one period
     for (int i = 1; i < pb.nx; ++i)
@@ -1774,6 +1803,64 @@ struct Impl : ImplBase {
         H2D(d_ys64, grid_y.data(), pb.ny * sizeof(double));
       }
     }
+    return PDHG_OK;
+  }
+  // the kernel parameters of this context's T rows (samples, positions, noise and records are the caller's)
+  TrajP<R> traj_params(const pdhg_traj_opts& o, int noise_mode) const {
+    const int nd = pb.ndim;
+    TrajP<R> a{};
+    a.nx = pb.nx;
+    a.ny = pb.ny;
+    a.T = pb.T;
+    a.step0 = 0;
+    a.bcx = pb.bc_x;
+    a.method = o.method;
+    a.center_x = o.center_x ? 1 : 0;
+    a.center_y = o.center_y ? 1 : 0;
+    a.noise_mode = noise_mode;
+    a.seed = o.seed;
+    a.Px = o.x_period;
+    a.Py = nd == 2 ? o.y_period : 1.0;
+    a.dt = pb.dt;
+    a.sq = std::sqrt(2 * pb.epsl * pb.dt);
+    a.inv_dx = 1.0 / pb.dx;
+    a.inv_dy = nd == 2 ? 1.0 / pb.dy : 0.0;
+    a.xs = d_xs64;
+    a.ys = d_ys64;
+    for (int s = 0; s < 2; ++s)
+      for (int k = 0; k < 4; ++k) a.alp[s][k] = kp.alp[s][k];
+    a.ctrl = kp.ctrl;
+    return a;
+  }
+  int launch_traj(const TrajP<R>& a) {
+    const dim3 grid((unsigned)((a.n + 255) / 256)), block(256);
+    if (pb.ndim == 1) return with_egno<2>([&](auto E) { return launch(k_traj_1d<R, decltype(E)::value>, grid, block, 0, a); });
+    return with_egno<3>([&](auto E) { return launch(k_traj_2d<R, decltype(E)::value>, grid, block, 0, a); });
+  }
+  // pdhg_slab_trajectories: this slab's T steps of a longer rollout, global steps [step0, step0 + T); every buffer is
+  // a device pointer used on the context's stream (noise and records indexed by global step, kernels_traj.hpp)
+  int slab_trajectories(const pdhg_traj_opts& o, int step0, unsigned long long n, const double* d_x_in,
+                        const double* d_noise, double* d_x_out, double* d_rec_x, double* d_rec_a) {
+    int rc;
+    if ((rc = traj_ready(o))) return rc;
+    TrajP<R> a = traj_params(o, pb.epsl > 0 ? (d_noise ? 1 : 2) : 0);
+    a.step0 = step0;
+    a.n = n;
+    a.s0 = (unsigned long long)o.sample_offset;
+    a.x_in = d_x_in;
+    a.noise = d_noise;
+    a.x_out = d_x_out;
+    a.rec_x = d_rec_x;
+    a.rec_a = d_rec_a;
+    return launch_traj(a);
+  }
+  int trajectories(const pdhg_traj_opts& o, const double* x_init, const double* noise, double* x_final, double* traj_x,
+                   double* traj_alp) {
+    if (slab || xslab)
+      return fail(PDHG_ERR_UNSUPPORTED, "trajectories need the whole window in one context (not a t-slab / x-slab)");
+    const int nd = pb.ndim, nc = n_ctrl(), T = pb.T;
+    int rc;
+    if ((rc = traj_ready(o))) return rc;
     const bool noisy = pb.epsl > 0;
     const size_t n = (size_t)o.n_sample;
     const size_t w_x = (size_t)nd, w_a = (size_t)nc;   // doubles per sample and row
@@ -1796,27 +1883,7 @@ struct Impl : ImplBase {
     if (noisy && noise) d_noise = d_next, d_next += (size_t)T * m * w_x;
     if (traj_x) d_rx = d_next, d_next += (size_t)(T + 1) * m * w_x;
     if (traj_alp) d_ra = d_next;
-    TrajP<R> a{};
-    a.nx = pb.nx;
-    a.ny = pb.ny;
-    a.T = T;
-    a.bcx = pb.bc_x;
-    a.method = o.method;
-    a.center_x = o.center_x ? 1 : 0;
-    a.center_y = o.center_y ? 1 : 0;
-    a.noise_mode = noisy ? (noise ? 1 : 2) : 0;
-    a.seed = o.seed;
-    a.Px = Px;
-    a.Py = Py;
-    a.dt = pb.dt;
-    a.sq = std::sqrt(2 * pb.epsl * pb.dt);
-    a.inv_dx = 1.0 / pb.dx;
-    a.inv_dy = nd == 2 ? 1.0 / pb.dy : 0.0;
-    a.xs = d_xs64;
-    a.ys = d_ys64;
-    for (int s = 0; s < 2; ++s)
-      for (int k = 0; k < 4; ++k) a.alp[s][k] = kp.alp[s][k];
-    a.ctrl = kp.ctrl;
+    TrajP<R> a = traj_params(o, noisy ? (noise ? 1 : 2) : 0);
     a.x_in = d_in;
     a.noise = d_noise;
     a.x_out = d_out;
@@ -1830,10 +1897,7 @@ struct Impl : ImplBase {
                                mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
       a.n = mc;
       a.s0 = (unsigned long long)o.sample_offset + c0;
-      const dim3 grid((unsigned)((mc + 255) / 256)), block(256);
-      if (nd == 1) rc = with_egno<2>([&](auto E) { return launch(k_traj_1d<R, decltype(E)::value>, grid, block, 0, a); });
-      else rc = with_egno<3>([&](auto E) { return launch(k_traj_2d<R, decltype(E)::value>, grid, block, 0, a); });
-      if (rc) return rc;
+      if ((rc = launch_traj(a))) return rc;
       if (x_final)
         HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, mc * w_x * sizeof(double), hipMemcpyDeviceToHost, stream));
       for (int j = 0; d_rx && j <= T; ++j)
@@ -1856,6 +1920,7 @@ struct Impl : ImplBase {
   static constexpr int kRepYpl = sizeof(P) == 8 ? 2 : 4;
   double* rep_partials = nullptr;   // [rows of the largest launch: report_rows_cap][kNumSums], then the folded row
   int rep_cap = 0;
+  P* rep_phi_halo = nullptr;        // t-slab with j0 > 0: phi row 0 = the previous slab's phi row T, staged per call
   struct RepGrid {
     dim3 grid, block;
     int rows, jchunk;
@@ -1896,13 +1961,16 @@ struct Impl : ImplBase {
     if (pb.ndim == 2 && pp.report_tile) return report_tiles() * report_chunks(pb.T);
     return report_grid(pb.T).rows;
   }
-  int report_ready() {
-    if (slab || xslab)
+  // slab_call: through pdhg_slab_report / pdhg_slab_report_rows, whose caller supplies the halo planes
+  int report_ready(bool slab_call = false) {
+    if (xslab || (slab && !slab_call))
       return fail(PDHG_ERR_UNSUPPORTED, "the report needs the whole window in one context (a t-slab's / x-slab's "
                                         "halo rows are not resident)");
     if (!rep_partials) {
       rep_cap = report_rows_cap();
       if (int rc = alloc(&rep_partials, (size_t)(rep_cap + 1) * kNumSums)) return rc;
+      if (slab && slab_j0 > 0)
+        if (int rc = alloc(&rep_phi_halo, plane())) return rc;
     }
     return PDHG_OK;
   }
@@ -1911,7 +1979,7 @@ struct Impl : ImplBase {
     const RepGrid g = report_grid(j1 - j0);
     if (g.rows > rep_cap) return fail(PDHG_ERR_STATE, "report table of %d rows for a launch of %d", rep_cap, g.rows);
     *rows = g.rows;
-    const RepP rp{j0, j1, g.jchunk, d_hj, d_cont, rep_partials};
+    const RepP rp{j0, j1, g.jchunk, d_hj, d_cont, rep_partials, rep_phi_halo};
     if (pb.ndim == 1)
       return with_egno<2>([&](auto E) { return launch(k_report_1d<R, decltype(E)::value>, g.grid, g.block, 0, kp, rp); });
     if (pp.report_tile)
@@ -1933,33 +2001,33 @@ struct Impl : ImplBase {
     double h[kNumSums];
     HIP_TRY(hipMemcpyAsync(h, d_out, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    pdhg_report r{};
-    r.n_points = (long long)pb.T * pb.nx * pb.ny;
-    r.n_nonfinite = (long long)h[6];
-    r.n_rho_zero = (long long)h[7];
-    const double n = (double)(r.n_points - r.n_nonfinite);
-    if (n > 0) {
-      r.hj_l1 = h[0] / n;
-      r.hj_l2 = std::sqrt(h[1] / n);
-      r.compl_l1 = h[3] == 0.0 ? 0.0 : h[2] / h[3];
-      r.rho_mean = h[3] / n;
-      r.cont_l1 = h[4] / n;
-      r.cont_l2 = std::sqrt(h[5] / n);
-      r.hj_max = h[8];
-      r.hj_pos_max = h[9];
-      r.hj_active_max = h[10];
-      r.cont_max = h[11];
-      r.rho_max = h[12];
-      r.rho_min = -h[13];
-      r.phi_max = h[14];
-      r.phi_min = -h[15];
-    } else {
-      const double nan = std::nan("");
-      r.hj_l1 = r.hj_l2 = r.hj_max = r.hj_pos_max = r.hj_active_max = r.compl_l1 = nan;
-      r.cont_l1 = r.cont_l2 = r.cont_max = r.rho_min = r.rho_max = r.rho_mean = r.phi_min = r.phi_max = nan;
-    }
-    *out = r;
+    *out = report_from_sums(h, (long long)pb.T * pb.nx * pb.ny);
     return PDHG_OK;
+  }
+  // ---- the report on a t-slab (pdhg_slab_report / pdhg_slab_report_rows; pdhg_multi.hpp folds the slabs) ----
+  // phi_prev: the previous slab's phi row T (device, phi's type), staged into the report's own plane; the caller has
+  // delivered the next slab's fresh rho row 0 through plane_in(0).  Everything is enqueued on the context's stream.
+  int slab_report_halo(const void* phi_prev) {
+    if (int rc = report_ready(true)) return rc;
+    if (slab_j0 == 0) return PDHG_OK;
+    if (!phi_prev) return fail(PDHG_ERR_ARG, "a slab after the first needs the previous slab's phi row T");
+    HIP_TRY(hipMemcpyAsync(rep_phi_halo, phi_prev, plane() * sizeof(P), hipMemcpyDeviceToDevice, stream));
+    return PDHG_OK;
+  }
+  int slab_report(const void* phi_prev, double* d_sums) {
+    int rc, rows = 0;
+    if ((rc = slab_report_halo(phi_prev))) return rc;
+    ProfScope ps(this, "report");
+    if ((rc = launch_report(0, pb.T, nullptr, nullptr, &rows))) return rc;
+    return launch(k_report_finalize, dim3(1), dim3(1024), 0, (const double*)rep_partials, rows, d_sums);
+  }
+  int slab_report_rows(const void* phi_prev, int row0, int nrows, double* d_hj, double* d_cont) {
+    int rc, rows = 0;
+    if (row0 >= pb.T || nrows > pb.T - row0)
+      return fail(PDHG_ERR_ARG, "%d rows from row %d outside the slab's residual rows [0, %d)", nrows, row0, pb.T);
+    if ((rc = slab_report_halo(phi_prev))) return rc;
+    if (!d_hj && !d_cont) return PDHG_OK;
+    return launch_report(row0, row0 + nrows, d_hj, d_cont, &rows);
   }
   int report_rows(int row0, int nrows, double* hj, double* cont) {
     int rc, rows = 0;

@@ -15,6 +15,10 @@
 //   k_report_2d / k_report_1d   one thread per point, neighbours through nb_index: any shape and bc
 //   k_report_tile_2d            8 rows x (64 YPL) columns per workgroup marching over t (nx % 8 == 0, ny % 256 == 0,
 //                               bc_y periodic, bc_x periodic or Neumann): every array is read once per point
+// A t-slab (KP::slab, rows [j0, j0 + T) of Tg; pdhg_slab_report) holds two of a pass's planes elsewhere: rho row T is
+// the next slab's rho row 0 (KP::rho_halo, delivered by the caller; zero on the window's last slab, which alone adds
+// c_on_rho / dt) and, for j0 > 0, phi row 0 is the previous slab's phi row T: the iteration maintains phi_bar row 0
+// only, so it is read from RepP::phi_halo, a plane the report owns, never written into the slab's phi.
 #pragma once
 #include <type_traits>
 #include "kernels_1d.hpp"
@@ -32,6 +36,7 @@ struct RepP {
   double* hj;         // [j1 - j0][nx][ny] field rows, or null
   double* cont;       // likewise
   double* partials;   // [workgroups][kNumSums]
+  const void* phi_halo;   // t-slab with KP::j0 > 0: phi row 0 (the previous slab's phi row T) [nx][ny] in phi's type
 };
 
 struct RepAcc {
@@ -180,7 +185,7 @@ __global__ void __launch_bounds__(256) k_report_2d(KP<R> p, PhiX<R, P> px, RepP 
     const int x = row - j * nx;
     const size_t c = (size_t)x * ny + y;
     const P* f1 = phi + (size_t)(j + 1) * plane;
-    const P* f0 = phi + (size_t)j * plane;
+    const P* f0 = (j == 0 && p.j0 > 0) ? static_cast<const P*>(rp.phi_halo) : phi + (size_t)j * plane;
     const int xm = nb_index(x - 1, nx, p.bcx), xp = nb_index(x + 1, nx, p.bcx);
     const P pc = f1[c];
     const P pxm = (xm >= 0) ? f1[(size_t)xm * ny + y] : (P)0;
@@ -299,13 +304,13 @@ __global__ void __launch_bounds__(512) k_report_tile_2d(KP<R> p, PhiX<R, P> px, 
   };
   auto load_rho = [&](int j) {
     Rho q;
-    if (j < T) {
-      const R* rj = rho + (size_t)j * plane;
+    if (j < T || !p.last_slab) {   // uniform; row T of a slab: the next slab's row 0
+      const R* rj = (j < T) ? rho + (size_t)j * plane : p.rho_halo;
       q.c = ldy<YPL>(rj + rxc + y);
       q.h = has_h ? ldy<YPL>(rj + rxh + y) : zy<R, YPL>();
       q.el = rj[rxc + ywm];
       q.er = rj[rxc + ywp];
-    } else {   // rho_T = 0 (Dt_increasedim)
+    } else {   // the window's rho_T = 0 (Dt_increasedim)
       q.c = q.h = zy<R, YPL>();
       q.el = q.er = (R)0;
     }
@@ -334,7 +339,9 @@ __global__ void __launch_bounds__(512) k_report_tile_2d(KP<R> p, PhiX<R, P> px, 
   RepAcc acc;
   acc.init();
   if (j0 < j1) {
-    VP f0 = ldy<YPL>(phi + (size_t)j0 * plane + rxc + y);   // phi row j
+    // phi row j; a slab's row 0 from the report's halo plane (uniform)
+    const P* f0p = (j0 == 0 && p.j0 > 0) ? static_cast<const P*>(rp.phi_halo) : phi + (size_t)j0 * plane;
+    VP f0 = ldy<YPL>(f0p + rxc + y);
     Rho rj = load_rho(j0);                                  // rho row j
     In cur = load(j0), nxt = cur;
     // One loop body for every step: a row's values do not depend on where its step falls in a workgroup's chunk
@@ -390,7 +397,7 @@ __global__ void __launch_bounds__(512) k_report_tile_2d(KP<R> p, PhiX<R, P> px, 
         e2 = m2f<EGNO, R>(rj.er, cur.aer, ayp);
       }
       const R m1yl = lane_from_prev(m1y[YPL - 1], e1), m2yr = lane_from_next(m2y[0], e2);
-      const bool last = (j == T - 1);
+      const bool last = (j == T - 1) && p.last_slab;   // the window's last row
       const size_t oo = (size_t)(j - rp.j0) * plane + rxc + y;
 #pragma unroll
       for (int e = 0; e < YPL; ++e) {

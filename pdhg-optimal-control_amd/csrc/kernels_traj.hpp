@@ -17,6 +17,10 @@
 //   u2 =  ((r2 << 32 | r3) >> 11)      * 2^-53   in [0, 1)
 //   z(axis 2p) = sqrt(-2 ln u1) cos(2 pi u2),  z(axis 2p+1) = sqrt(-2 ln u1) sin(2 pi u2)
 // a pure function of (seed, sample, step, axis): independent of the launch shape and of the chunking.
+//
+// A t-slab (pdhg_slab_trajectories) marches its own T rows of a longer rollout: local step ind is global step
+// step0 + ind -- the Philox step word, the row of a staged noise array and the row of the records, which are the
+// whole rollout's arrays.  step0 = 0 on a context that holds the whole window.
 #pragma once
 #include "params.hpp"
 
@@ -25,6 +29,7 @@ namespace pdhg {
 template <typename R>
 struct TrajP {
   int nx, ny, T;
+  int step0;                 // global step of local step 0 (t-slab: the rows of the rollout already marched)
   int bcx;                   // 0 periodic, 1 Neumann (edge value outside the grid); y is periodic
   int method;                // 0 linear, 1 nearest
   int center_x, center_y;    // the period cell is [-P/2, P/2) instead of [0, P)
@@ -39,10 +44,10 @@ struct TrajP {
   const R* alp[2][4];        // both buffer sets; the kernel picks ctrl->cur
   const Ctrl* ctrl;
   const double* x_in;        // [n][ndim]
-  const double* noise;       // [T][n][ndim] (noise_mode 1)
+  const double* noise;       // [steps][n][ndim] by global step (noise_mode 1)
   double* x_out;             // [n][ndim]
-  double* rec_x;             // [T+1][n][ndim] or null
-  double* rec_a;             // [T][n][n_ctrl] or null
+  double* rec_x;             // [steps+1][n][ndim] by global step, or null; row 0 is written where step0 == 0
+  double* rec_a;             // [steps][n][n_ctrl] by global step, or null
 };
 
 // ---- Philox4x32-10 (Salmon et al., SC'11) ----
@@ -142,17 +147,18 @@ __global__ void __launch_bounds__(256) k_traj_2d(TrajP<R> p) {
   for (int a = 0; a < NA; ++a) A[a] = cur ? p.alp[1][a] : p.alp[0][a];   // no dynamic index into the argument block
   const size_t npl = (size_t)p.nx * (size_t)p.ny;
   double x = p.x_in[2 * s], y = p.x_in[2 * s + 1];
-  if (p.rec_x) {
+  if (p.rec_x && p.step0 == 0) {
     p.rec_x[2 * s] = x;
     p.rec_x[2 * s + 1] = y;
   }
   for (int ind = 0; ind < p.T; ++ind) {
     const size_t row = (size_t)(p.T - 1 - ind) * npl;
+    const int step = p.step0 + ind;
     const TrajCell cx = traj_locate(x, p.xs, p.nx, p.Px, p.inv_dx, p.bcx, p.center_x);
     const TrajCell cy = traj_locate(y, p.ys, p.ny, p.Py, p.inv_dy, 0, p.center_y);
     double nz0 = 0.0, nz1 = 0.0;
     if (p.noise_mode == 1) {
-      const size_t o = ((size_t)ind * p.n + s) * 2;
+      const size_t o = ((size_t)step * p.n + s) * 2;
       nz0 = p.noise[o];
       nz1 = p.noise[o + 1];
     }
@@ -181,9 +187,9 @@ __global__ void __launch_bounds__(256) k_traj_2d(TrajP<R> p) {
       for (int a = 0; a < NA; ++a)
         al[a] = w00 * (double)v[a][0] + w10 * (double)v[a][1] + w01 * (double)v[a][2] + w11 * (double)v[a][3];
     }
-    if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, ind, 0, nz0, nz1);
+    if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, step, 0, nz0, nz1);
     if (p.rec_a) {
-      double* ra = p.rec_a + ((size_t)ind * p.n + s) * NC;
+      double* ra = p.rec_a + ((size_t)step * p.n + s) * NC;
       ra[0] = al[0] + al[1];
       if constexpr (NC == 2) ra[1] = al[2] + al[3];
     }
@@ -205,7 +211,7 @@ __global__ void __launch_bounds__(256) k_traj_2d(TrajP<R> p) {
       y = y + p.sq * nz1;
     }
     if (p.rec_x) {
-      double* rx = p.rec_x + ((size_t)(ind + 1) * p.n + s) * 2;
+      double* rx = p.rec_x + ((size_t)(step + 1) * p.n + s) * 2;
       rx[0] = x;
       rx[1] = y;
     }
@@ -228,12 +234,13 @@ __global__ void __launch_bounds__(256) k_traj_1d(TrajP<R> p) {
   const R* __restrict__ A1 = cur ? p.alp[1][1] : p.alp[0][1];
   const double* __restrict__ g = p.xs;
   double x = p.x_in[s];
-  if (p.rec_x) p.rec_x[s] = x;
+  if (p.rec_x && p.step0 == 0) p.rec_x[s] = x;
   for (int ind = 0; ind < p.T; ++ind) {
     const size_t row = (size_t)(p.T - 1 - ind) * (size_t)n;
+    const int step = p.step0 + ind;
     const double xm = traj_pmod(x, p.Px);
     double nz = 0.0, nz_unused;
-    if (p.noise_mode == 1) nz = p.noise[(size_t)ind * p.n + s];
+    if (p.noise_mode == 1) nz = p.noise[(size_t)step * p.n + s];
     int j = (int)fmin(fmax((xm - g[0]) * p.inv_dx, 0.0), (double)(n - 1));
     double a1, a2;
     if (p.method == 1) {
@@ -263,13 +270,13 @@ __global__ void __launch_bounds__(256) k_traj_1d(TrajP<R> p) {
       a1 = (double)v10 + w * ((double)v11 - (double)v10);
       a2 = (double)v20 + w * ((double)v21 - (double)v20);
     }
-    if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, ind, 0, nz, nz_unused);
-    if (p.rec_a) p.rec_a[(size_t)ind * p.n + s] = a1 + a2;
+    if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, step, 0, nz, nz_unused);
+    if (p.rec_a) p.rec_a[(size_t)step * p.n + s] = a1 + a2;
     const double a = traj_coef(xm);
     const double vel = fpos(fval<double, EGNO>(a1, a)) + fneg(fval<double, EGNO>(a2, a));
     x = x + vel * p.dt;
     if (p.noise_mode) x = x + p.sq * nz;
-    if (p.rec_x) p.rec_x[(size_t)(ind + 1) * p.n + s] = x;
+    if (p.rec_x) p.rec_x[(size_t)(step + 1) * p.n + s] = x;
   }
   p.x_out[s] = x;
 }

@@ -427,8 +427,8 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
   }
   // the report's tile kernel: whole 8-row x 256-column tiles, y periodic, x periodic or Neumann (its halo rows wrap
   // or clamp); single contexts (a slab's halo rows are not resident: the report refuses those)
-  pl.report_tile = is2d && nx % 8 == 0 && ny % 256 == 0 && pb.bc_y == 0 && (pb.bc_x == 0 || pb.bc_x == 1) && !slab &&
-                   !xslab && tn.report_tile.value_or(1) != 0;
+  pl.report_tile = is2d && nx % 8 == 0 && ny % 256 == 0 && pb.bc_y == 0 && (pb.bc_x == 0 || pb.bc_x == 1) && !xslab &&
+                   tn.report_tile.value_or(1) != 0;   // (a t-slab's pass: pdhg_slab_report)
   pl.report_wgs = tn.report_wgs;
   pl.g_outer = tn.g_outer;
   pl.head_xrun = tn.head_xrun;

@@ -481,6 +481,30 @@ int pdhg_slab_plane_in(pdhg_ctx* ctx, int which, const void* src) {
   if (!src) return fail(PDHG_ERR_ARG, "null plane");
   return slab_dispatch(ctx, [&](auto& im) { return im.slab_plane_in(which, src); });
 }
+/* the report and the rollout on a t-slab: the pieces pdhg_multi_report_state / _report_rows / _trajectories and
+ * pdhg_amd.slab.SlabRunner.report chain across slabs */
+int pdhg_slab_report(pdhg_ctx* ctx, const void* phi_prev_rowT, double* sums) {
+  if (!sums) return fail(PDHG_ERR_ARG, "null sums");
+  return slab_dispatch(ctx, [&](auto& im) { return im.slab_report(phi_prev_rowT, sums); });
+}
+int pdhg_slab_report_rows(pdhg_ctx* ctx, const void* phi_prev_rowT, int row0_local, int nrows, double* d_hj,
+                          double* d_cont) {
+  if (row0_local < 0 || nrows < 1) return fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0_local, nrows);
+  return slab_dispatch(ctx, [&](auto& im) { return im.slab_report_rows(phi_prev_rowT, row0_local, nrows, d_hj, d_cont); });
+}
+int pdhg_slab_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, int step0, long long n, const double* d_x_in,
+                           const double* d_noise, double* d_x_out, double* d_rec_x, double* d_rec_a) {
+  if (!opts || !d_x_in || !d_x_out) return fail(PDHG_ERR_ARG, "null opts, x_in or x_out");
+  if (n < 1 || step0 < 0) return fail(PDHG_ERR_ARG, "n must be >= 1 and step0 >= 0");
+  if (opts->sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
+  if (opts->method != 0 && opts->method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", opts->method);
+  if (!(opts->x_period > 0) || !(opts->y_period > 0)) return fail(PDHG_ERR_ARG, "periods must be > 0");
+  return slab_dispatch(ctx, [&](auto& im) {
+    if (step0 > im.slab_Tg - im.slab_j0 - im.pb.T)
+      return fail(PDHG_ERR_ARG, "step0 %d: the slabs after this one hold %d rows", step0, im.slab_Tg - im.slab_j0 - im.pb.T);
+    return im.slab_trajectories(*opts, step0, (unsigned long long)n, d_x_in, d_noise, d_x_out, d_rec_x, d_rec_a);
+  });
+}
 int pdhg_slab_status(pdhg_ctx* ctx, pdhg_stats* st) {
   if (!st) return fail(PDHG_ERR_ARG, "null stats");
   return phase_dispatch(ctx, [&](auto& im) { return im.slab_status(st); });

@@ -528,6 +528,176 @@ struct pdhg_multi {
     return PDHG_OK;
   }
 
+  // ---------------- solution report and trajectories over the slabs (include/pdhg.h) ----------------
+  // Read-only on the states, phi_bar and the loop control.  The exchange buffers rho_send / rho_recv / pb_send /
+  // pb_recv and the events b[r].rho / b[r].pb are free between iterations (every step rewrites or re-records them
+  // before it uses them) and carry the report's planes; every call drains the slab streams before it returns.
+  std::vector<double*> rep_sums;   // per slab: its kNumSums report row (allocated by the first report)
+  // full barrier; rho row 0 of slab r+1 -> slab r's halo (what the next step's residual would deliver: rho does not
+  // change in between); phi row T of slab r-1 -> b[r].pb_recv, the phi_prev plane of slab r's pass
+  int report_halos() {
+    int rc;
+    const size_t pbytes = sp * es;
+    if ((rc = full_barrier())) return rc;
+    for (int r = 0; r < P; ++r)
+      if ((rc = pdhg_slab_plane_out(s[r], 0, b[r].rho_send)) || (rc = pdhg_slab_plane_out(s[r], 4, b[r].pb_send)) ||
+          (rc = rec(b[r].rho, r, st[r])))
+        return rc;
+    for (int r = 0; r < P; ++r) {
+      if (r + 1 < P && ((rc = wait(r, st[r], b[r + 1].rho)) ||
+                        (rc = copy(r, st[r], b[r].rho_recv, r + 1, b[r + 1].rho_send, pbytes)) ||
+                        (rc = pdhg_slab_plane_in(s[r], 0, b[r].rho_recv))))
+        return rc;
+      if (r > 0 && ((rc = wait(r, st[r], b[r - 1].rho)) ||
+                    (rc = copy(r, st[r], b[r].pb_recv, r - 1, b[r - 1].pb_send, pbytes))))
+        return rc;
+    }
+    return PDHG_OK;
+  }
+  const void* phi_prev(int r) const { return r > 0 ? b[r].pb_recv : nullptr; }
+  int report_state(pdhg_report* out) {
+    int rc;
+    if (rep_sums.empty()) {
+      std::vector<double*> t(P, nullptr);
+      for (int r = 0; r < P; ++r)
+        if ((rc = alloc(r, &t[r], (size_t)kNumSums))) return rc;
+      rep_sums.swap(t);
+    }
+    if ((rc = report_halos())) return rc;
+    for (int r = 0; r < P; ++r)   // every slab's pass on its own stream
+      if ((rc = pdhg_slab_report(s[r], phi_prev(r), rep_sums[r]))) return rc;
+    std::vector<double> h((size_t)P * kNumSums);
+    for (int r = 0; r < P; ++r) {
+      if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
+      HIP_TRY(hipMemcpyAsync(h.data() + (size_t)r * kNumSums, rep_sums[r], kNumSums * sizeof(double),
+                             hipMemcpyDeviceToHost, st[r]));
+    }
+    if ((rc = full_barrier())) return rc;
+    // the P rows in slab order: sums added, extrema maximised (the minima are stored negated: k_report_finalize)
+    double f[kNumSums];
+    for (int c = 0; c < kNumSums; ++c) {
+      double t = h[c];
+      for (int r = 1; r < P; ++r) {
+        const double v = h[(size_t)r * kNumSums + c];
+        t = c < pdhg::kRepSums ? t + v : std::fmax(t, v);
+      }
+      f[c] = t;
+    }
+    *out = report_from_sums(f, (long long)pb.T * pb.nx * pb.ny);
+    return PDHG_OK;
+  }
+  // global rows [row0, row0 + nrows): per slab its part of the range, staged on the slab's device in row chunks
+  int report_rows(int row0, int nrows, double* hj, double* cont) {
+    int rc;
+    if (row0 >= pb.T || nrows > pb.T - row0)
+      return fail(PDHG_ERR_ARG, "%d rows from row %d outside the residual rows [0, %d)", nrows, row0, pb.T);
+    if (!hj && !cont) return PDHG_OK;
+    if ((rc = report_halos())) return rc;
+    const size_t npl = (size_t)pb.nx * pb.ny, per = npl * sizeof(double) * ((hj ? 1 : 0) + (cont ? 1 : 0));
+    for (int r = 0; r < P; ++r) {
+      const int a = std::max(row0, j0[r]), e = std::min(row0 + nrows, j1[r]);
+      if (a >= e) continue;
+      const int m = (int)std::min<size_t>((size_t)(e - a), std::max<size_t>(kRowsBudget / per, 1));   // rows per chunk
+      if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
+      struct Tmp {   // the chunk planes: one allocation, freed on every way out
+        double* p = nullptr;
+        ~Tmp() { if (p) hipFree(p); }
+      } tmp;
+      if (hipMalloc((void**)&tmp.p, (size_t)m * per) != hipSuccess)
+        return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the report rows failed", (size_t)m * per);
+      double* d_hj = hj ? tmp.p : nullptr;
+      double* d_cont = cont ? tmp.p + (hj ? (size_t)m * npl : 0) : nullptr;
+      for (int c0 = a; c0 < e; c0 += m) {
+        const int mc = std::min(m, e - c0);
+        if ((rc = pdhg_slab_report_rows(s[r], phi_prev(r), c0 - j0[r], mc, d_hj, d_cont))) return rc;
+        const size_t nb = (size_t)mc * npl * sizeof(double);
+        if (hj) HIP_TRY(hipMemcpyAsync(hj + (size_t)(c0 - row0) * npl, d_hj, nb, hipMemcpyDeviceToHost, st[r]));
+        if (cont) HIP_TRY(hipMemcpyAsync(cont + (size_t)(c0 - row0) * npl, d_cont, nb, hipMemcpyDeviceToHost, st[r]));
+        HIP_TRY(hipStreamSynchronize(st[r]));   // the chunk planes are reused
+      }
+    }
+    return full_barrier();
+  }
+  // The rollout through the whole window: control time runs against PDE time, so a chunk of samples enters the LAST
+  // slab at global step 0 and marches through slabs P-1 ... 0; slab r starts when slab r+1's positions have arrived
+  // (copy() on slab r's stream after slab r+1's event: device to device).  One chunk buffer per distinct device, laid
+  // out as the single context's (positions in / out, noise [Tg], records [Tg + 1] / [Tg], all by global step): a slab
+  // uploads the noise rows and returns the record rows of its own steps.
+  int trajectories(const pdhg_traj_opts& o, const double* x_init, const double* noise, double* x_final,
+                   double* traj_x, double* traj_alp) {
+    int rc;
+    const int T = pb.T;
+    const bool noisy = pb.epsl > 0;
+    const size_t n = (size_t)o.n_sample, w_x = 2, w_a = (size_t)nc;
+    const size_t per = sizeof(double) * (2 * w_x + (noisy && noise ? (size_t)T * w_x : 0) +
+                                         (traj_x ? (size_t)(T + 1) * w_x : 0) + (traj_alp ? (size_t)T * w_a : 0));
+    size_t m = std::max<size_t>(kSampleBudget / per, 256) / 256 * 256;   // whole workgroups per chunk
+    m = std::min(m, n);
+    struct Tmp {
+      std::vector<std::pair<int, double*>> p;   // (device, buffer)
+      ~Tmp() {
+        for (auto& q : p) {
+          hipSetDevice(q.first);
+          hipFree(q.second);
+        }
+      }
+    } tmp;
+    std::vector<double*> base(P, nullptr);
+    if ((rc = full_barrier())) return rc;
+    for (int r = 0; r < P; ++r) {
+      for (auto& q : tmp.p)
+        if (q.first == dev[r]) base[r] = q.second;
+      if (base[r]) continue;
+      if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
+      if (hipMalloc((void**)&base[r], m * per) != hipSuccess)
+        return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the trajectory chunk failed", m * per);
+      tmp.p.push_back({dev[r], base[r]});
+    }
+    const size_t o_out = m * w_x, o_noise = 2 * m * w_x, o_rx = o_noise + (noisy && noise ? (size_t)T * m * w_x : 0),
+                 o_ra = o_rx + (traj_x ? (size_t)(T + 1) * m * w_x : 0);
+    for (size_t c0 = 0; c0 < n; c0 += m) {
+      const size_t mc = std::min(m, n - c0);
+      pdhg_traj_opts oc = o;
+      oc.n_sample = (long long)mc;
+      oc.sample_offset = o.sample_offset + (long long)c0;
+      int step0 = 0;
+      for (int r = P - 1; r >= 0; --r) {
+        const int Tr = j1[r] - j0[r];
+        double* d_in = base[r];
+        double* d_out = base[r] + o_out;
+        double* d_noise = noisy && noise ? base[r] + o_noise : nullptr;
+        double* d_rx = traj_x ? base[r] + o_rx : nullptr;
+        double* d_ra = traj_alp ? base[r] + o_ra : nullptr;
+        if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
+        if (r == P - 1) {
+          HIP_TRY(hipMemcpyAsync(d_in, x_init + c0 * w_x, mc * w_x * sizeof(double), hipMemcpyHostToDevice, st[r]));
+        } else if ((rc = wait(r, st[r], b[r + 1].pb)) ||
+                   (rc = copy(r, st[r], d_in, r + 1, base[r + 1] + o_out, mc * w_x * sizeof(double)))) {
+          return rc;
+        }
+        for (int j = step0; d_noise && j < step0 + Tr; ++j)
+          HIP_TRY(hipMemcpyAsync(d_noise + (size_t)j * mc * w_x, noise + ((size_t)j * n + c0) * w_x,
+                                 mc * w_x * sizeof(double), hipMemcpyHostToDevice, st[r]));
+        if ((rc = pdhg_slab_trajectories(s[r], &oc, step0, (long long)mc, d_in, d_noise, d_out, d_rx, d_ra)) ||
+            (rc = rec(b[r].pb, r, st[r])))
+          return rc;
+        for (int j = step0 == 0 ? 0 : step0 + 1; d_rx && j <= step0 + Tr; ++j)
+          HIP_TRY(hipMemcpyAsync(traj_x + ((size_t)j * n + c0) * w_x, d_rx + (size_t)j * mc * w_x,
+                                 mc * w_x * sizeof(double), hipMemcpyDeviceToHost, st[r]));
+        for (int j = step0; d_ra && j < step0 + Tr; ++j)
+          HIP_TRY(hipMemcpyAsync(traj_alp + ((size_t)j * n + c0) * w_a, d_ra + (size_t)j * mc * w_a,
+                                 mc * w_a * sizeof(double), hipMemcpyDeviceToHost, st[r]));
+        if (r == 0 && x_final)
+          HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, mc * w_x * sizeof(double), hipMemcpyDeviceToHost, st[r]));
+        step0 += Tr;
+      }
+      if ((rc = full_barrier())) return rc;   // the chunk buffers are reused
+    }
+    return PDHG_OK;
+  }
+  // the staging budgets of the single context (ctx_impl.hpp kReportBudget / kTrajBudget)
+  static constexpr size_t kRowsBudget = Impl<float>::kReportBudget, kSampleBudget = Impl<float>::kTrajBudget;
+
   // total ms between marks [m0, m1) over the recorded steps
   int phase_ms(int m0, int m1, double* ms, int* n) {
     *ms = 0.0;
@@ -626,6 +796,26 @@ int pdhg_multi_info(pdhg_multi* m, const char* key, int* value) {
     return slab_device(m->s[r], value);
   } else return fail(PDHG_ERR_ARG, "unknown key '%s'", key);
   return PDHG_OK;
+}
+int pdhg_multi_report_state(pdhg_multi* m, pdhg_report* out) {
+  MULTI_GET(m);
+  if (!out) return fail(PDHG_ERR_ARG, "null report");
+  return m->report_state(out);
+}
+int pdhg_multi_report_rows(pdhg_multi* m, int row0, int nrows, double* hj, double* cont) {
+  MULTI_GET(m);
+  if (row0 < 0 || nrows < 1) return fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0, nrows);
+  return m->report_rows(row0, nrows, hj, cont);
+}
+int pdhg_multi_trajectories(pdhg_multi* m, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
+                            double* x_final, double* traj_x, double* traj_alp) {
+  MULTI_GET(m);
+  if (!opts || !x_init) return fail(PDHG_ERR_ARG, "null opts or x_init");
+  if (opts->n_sample < 1) return fail(PDHG_ERR_ARG, "n_sample must be >= 1");
+  if (opts->sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
+  if (opts->method != 0 && opts->method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", opts->method);
+  if (!(opts->x_period > 0) || !(opts->y_period > 0)) return fail(PDHG_ERR_ARG, "periods must be > 0");
+  return m->trajectories(*opts, x_init, noise, x_final, traj_x, traj_alp);
 }
 int pdhg_multi_profile(pdhg_multi* m, int enable) {
   MULTI_GET(m);

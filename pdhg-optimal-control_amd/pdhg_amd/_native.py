@@ -35,13 +35,16 @@ EXPORTS = (
     "pdhg_slab_dual_finalize", "pdhg_slab_outer", "pdhg_slab_outer_finalize", "pdhg_slab_plane_out",
     "pdhg_slab_plane_in", "pdhg_slab_status", "pdhg_slab_part_modes", "pdhg_slab_forward_part",
     "pdhg_slab_carry_out_part", "pdhg_slab_fixup_nb_part", "pdhg_slab_backward_part", "pdhg_slab_update",
+    # ... the report and the trajectories slab by slab
+    "pdhg_slab_report", "pdhg_slab_report_rows", "pdhg_slab_trajectories",
     # x-slab decomposition (multi-GPU for T = 1 windows)
     "pdhg_create_xslab", "pdhg_xslab_layout", "pdhg_xslab_sizes", "pdhg_xslab_halo_out", "pdhg_xslab_halo_in",
     "pdhg_xslab_residual", "pdhg_xslab_wire", "pdhg_xslab_precond", "pdhg_xslab_update",
     # multi-device context (one host thread, t-slabs over a device list)
     "pdhg_create_multi", "pdhg_multi_destroy", "pdhg_multi_set_state", "pdhg_multi_get_state",
     "pdhg_multi_iterate", "pdhg_multi_set_stop_rules", "pdhg_multi_synchronize", "pdhg_multi_info",
-    "pdhg_multi_profile", "pdhg_multi_phase_ms", "pdhg_multi_init_state", "pdhg_build_id",
+    "pdhg_multi_profile", "pdhg_multi_phase_ms", "pdhg_multi_init_state",
+    "pdhg_multi_report_state", "pdhg_multi_report_rows", "pdhg_multi_trajectories", "pdhg_build_id",
 )
 
 
@@ -181,6 +184,10 @@ def load():
                                     ctypes.c_int),
         "pdhg_slab_backward_part": ([P, ctypes.c_double, ctypes.c_int, ctypes.c_int], ctypes.c_int),
         "pdhg_slab_update": ([P, ctypes.c_double, P], ctypes.c_int),
+        "pdhg_slab_report": ([P, P, P], ctypes.c_int),
+        "pdhg_slab_report_rows": ([P, P, ctypes.c_int, ctypes.c_int, P, P], ctypes.c_int),
+        "pdhg_slab_trajectories": ([P, ctypes.POINTER(pdhg_traj_opts), ctypes.c_int, ctypes.c_longlong, P, P, P, P, P],
+                                   ctypes.c_int),
         "pdhg_create_xslab": ([ctypes.POINTER(pdhg_problem), ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                ctypes.POINTER(P)], ctypes.c_int),
         "pdhg_xslab_layout": ([P] + [ctypes.POINTER(ctypes.c_int)] * 4, ctypes.c_int),
@@ -204,6 +211,9 @@ def load():
         "pdhg_multi_profile": ([P, ctypes.c_int], ctypes.c_int),
         "pdhg_multi_init_state": ([P, dp], ctypes.c_int),
         "pdhg_multi_phase_ms": ([P, ctypes.c_char_p, dp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
+        "pdhg_multi_report_state": ([P, ctypes.POINTER(pdhg_report)], ctypes.c_int),
+        "pdhg_multi_report_rows": ([P, ctypes.c_int, ctypes.c_int, dp, dp], ctypes.c_int),
+        "pdhg_multi_trajectories": ([P, ctypes.POINTER(pdhg_traj_opts), dp, dp, dp, dp, dp], ctypes.c_int),
         "pdhg_build_id": ([], ctypes.c_char_p),
     }
     missing = set(EXPORTS) - set(sig)

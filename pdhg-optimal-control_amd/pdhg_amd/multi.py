@@ -9,13 +9,17 @@ used by ``bench.py --gpus N``.  Arrays are the whole window in the reference lay
 
 The handle is a ``pdhg_multi*``, not a ``pdhg_ctx*``: this class therefore does not derive from
 PDHGContext, and offers only the whole-window calls the multi-device ABI has (state, iterate, stop rules,
-synchronize, info).  The library also rejects a foreign handle passed to a ``pdhg_ctx`` entry point.
+synchronize, info, and the two read-only passes over the resident state: report / residual_rows and
+trajectories, with PDHGContext's signatures and return values).  The library also rejects a foreign handle passed
+to a ``pdhg_ctx`` entry point.  Like the rest of this context, the two passes have been run with every slab on one
+device only (``devices=[0] * n``).
 """
 import ctypes
 
 import numpy as np
 
 from . import _native as N
+from .context import traj_arguments
 
 
 class MultiContext:
@@ -92,6 +96,35 @@ class MultiContext:
         return {"iters_run": st.iters_run, "status": st.status, "inner_last": st.inner_last,
                 "inner_total": st.inner_total, "err1": st.err1, "err2": st.err2, "err_inner": st.err_inner,
                 "nan_seen": st.nan_seen, "first_nan_iter": st.first_nan_iter}
+
+    # ---- read-only passes over the resident state (pdhg_multi_report_state / _report_rows / _trajectories) ----
+    def report(self):
+        """PDHGContext.report for the whole window: every slab's pass on its own device, the slabs' sums folded in
+        slab order (a repeated call returns the same bits)."""
+        r = N.pdhg_report()
+        N.check(self._lib.pdhg_multi_report_state(self._h, ctypes.byref(r)))
+        return {f: getattr(r, f) for f in N.REPORT_FIELDS}
+
+    def residual_rows(self, row0, nrows, hj=True, cont=True):
+        """PDHGContext.residual_rows over global rows [row0, row0 + nrows) (a range may span slabs)."""
+        f = lambda on: np.empty((int(nrows),) + self._space) if on and nrows >= 1 else None  # noqa: E731
+        h, c = f(hj), f(cont)
+        N.check(self._lib.pdhg_multi_report_rows(self._h, int(row0), int(nrows), N.dptr(h), N.dptr(c)))
+        return h, c
+
+    def trajectories(self, x_init, method, x_period, y_period=None, center=(False, False), noise=None, seed=0,
+                     record=("x", "alp"), sample_offset=0):
+        """PDHGContext.trajectories through the window's T rows: the samples march through the slabs from the last
+        to the first, handed on device to device.  (traj_alp [T, n, n_ctrl], traj_x [T+1, n, 2], x_final [n, 2])."""
+        o, x0, noise, rec_x, rec_a = traj_arguments(2, self.T, x_init, method, x_period, y_period, center, noise,
+                                                    record, seed, sample_offset)
+        n = x0.shape[0]
+        x_final = np.empty((n, 2))
+        traj_x = np.empty((self.T + 1, n, 2)) if rec_x else None
+        traj_alp = np.empty((self.T, n, self.n_ctrl)) if rec_a else None
+        N.check(self._lib.pdhg_multi_trajectories(self._h, ctypes.byref(o), N.dptr(x0), N.dptr(noise),
+                                                  N.dptr(x_final), N.dptr(traj_x), N.dptr(traj_alp)))
+        return traj_alp, traj_x, x_final
 
     def set_stop_rules(self, converge=True, nan=True):
         N.check(self._lib.pdhg_multi_set_stop_rules(self._h, 1 if converge else 0, 1 if nan else 0))

@@ -133,6 +133,31 @@ def report_from_fields(hj, cont, rho, phi_rows):
     return d
 
 
+def fold_report_rows(rows):
+    """Fold per-slab rows of the report's 16 sums (pdhg_slab_report) in the order given -- slab order: columns 0-7
+    are sums (added), 8-15 extrema (maximised; the minima are stored negated).  A fixed order, unlike an all-reduce."""
+    rows = np.asarray(rows, dtype=np.float64).reshape(-1, 16)
+    out = rows[0].copy()
+    for row in rows[1:]:
+        out[:8] = out[:8] + row[:8]
+        out[8:] = np.fmax(out[8:], row[8:])
+    return out
+
+
+def report_from_sums(h, n_points):
+    """pdhg_report's fields from one folded row of the 16 sums over n_points points (the arithmetic of
+    pdhg_report_state / pdhg_multi_report_state, operation for operation)."""
+    h = [float(v) for v in h]
+    d = dict.fromkeys(REPORT_FIELDS, float("nan"))
+    d["n_points"], d["n_nonfinite"], d["n_rho_zero"] = int(n_points), int(h[6]), int(h[7])
+    n = float(d["n_points"] - d["n_nonfinite"])
+    if n > 0:
+        d.update(hj_l1=h[0] / n, hj_l2=float(np.sqrt(h[1] / n)), compl_l1=0.0 if h[3] == 0.0 else h[2] / h[3],
+                 rho_mean=h[3] / n, cont_l1=h[4] / n, cont_l2=float(np.sqrt(h[5] / n)), hj_max=h[8], hj_pos_max=h[9],
+                 hj_active_max=h[10], cont_max=h[11], rho_max=h[12], rho_min=-h[13], phi_max=h[14], phi_min=-h[15])
+    return d
+
+
 def report_from_arrays(phi, rho, alp, fns_dict, dt, dspatial, c_on_rho, epsl, x_arr, t_arr, bc, fields=False):
     """PDHGContext.report's dict from host arrays in the reference layouts (phi [T+1, ...], rho [T, ...], alp the tuple
     of 2 / 4 control arrays).  fields=True returns (dict, hj [T, ...], cont [T, ...]) -- what

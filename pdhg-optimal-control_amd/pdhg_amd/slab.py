@@ -28,7 +28,7 @@ import numpy as np
 from . import _native as N
 from .context import PDHGContext
 
-RHO_ROW0, PHIBAR_LAST, CARRY_DS, CARRY_LONG = 0, 1, 2, 3   # pdhg_slab_plane_out
+RHO_ROW0, PHIBAR_LAST, CARRY_DS, CARRY_LONG, PHI_LAST = 0, 1, 2, 3, 4   # pdhg_slab_plane_out
 RHO_HALO, PHIBAR_ROW0 = 0, 1                             # pdhg_slab_plane_in
 INTERIOR, EDGE = 1, 2                                    # pdhg_slab_residual / pdhg_slab_dual parts
 LONG_RANGE_DELTA = 2.0 ** -40     # modes whose slab gains are all below this exchange with neighbours only
@@ -166,6 +166,29 @@ class SlabContext(PhaseOps, PDHGContext):
 
     def plane_in(self, which, src):
         N.check(self._lib.pdhg_slab_plane_in(self._h, int(which), _ptr(src)))
+
+    # The solution report and the rollout slab by slab (pdhg_slab_report / _report_rows / _trajectories).  report(),
+    # residual_rows() and trajectories() inherited from PDHGContext stay refused on a slab: one slab alone does not hold
+    # the planes they read.  SlabRunner.report() chains the partial passes; SlabRunner has no trajectories yet.
+    def report_partial(self, phi_prev, sums):
+        """This slab's row of the report's 16 sums into the device tensor `sums` (float64[16]).  phi_prev: the
+        previous slab's phi row T (plane_out(PHI_LAST), a device plane of plane_dtype), None on the first slab; the
+        next slab's fresh rho row 0 must have been delivered (plane_in(RHO_HALO)) unless this is the last slab."""
+        N.check(self._lib.pdhg_slab_report(self._h, None if phi_prev is None else _ptr(phi_prev), _ptr(sums)))
+
+    def report_rows_partial(self, phi_prev, row0_local, nrows, hj=None, cont=None):
+        """Rows [row0_local, row0_local + nrows) of this slab's two fields into float64 device tensors
+        [nrows, nx, ny] (None: skipped); halos as report_partial."""
+        N.check(self._lib.pdhg_slab_report_rows(self._h, None if phi_prev is None else _ptr(phi_prev),
+                                                int(row0_local), int(nrows), None if hj is None else _ptr(hj),
+                                                None if cont is None else _ptr(cont)))
+
+    def trajectories_partial(self, opts, step0, n, x_in, noise, x_out, rec_x=None, rec_a=None):
+        """This slab's T steps of a rollout (global steps [step0, step0 + T)) on float64 device tensors indexed by
+        global step; opts: a pdhg_traj_opts whose sample_offset is the global index of x_in's sample 0."""
+        q = lambda t: None if t is None else _ptr(t)  # noqa: E731
+        N.check(self._lib.pdhg_slab_trajectories(self._h, ctypes.byref(opts), int(step0), int(n), _ptr(x_in), q(noise),
+                                                 _ptr(x_out), q(rec_x), q(rec_a)))
 
 
 def _ptr(t):
@@ -493,6 +516,29 @@ class SlabRunner:
             self._timed("allreduce", lambda: C.allreduce([b["sums"] for b in B]))
         for s, b in zip(S, B):
             s.outer_finalize(eps, k, b["sums"])
+
+    def report(self):
+        """PDHGContext.report for the whole window, on every rank the same dict: the rho halo (row 0 of slab r+1 ->
+        slab r) and the phi halo (row T of slab r-1 -> slab r's pass) go through the communicator's shifts, every
+        slab runs its partial pass, and the slabs' rows of 16 sums are gathered and folded in slab order -- an
+        all-reduce has no fixed order, so it is not used here.  Read-only on the states and the loop control."""
+        from .report import fold_report_rows, report_from_sums
+        torch = self.torch
+        S, B, C = self.slabs, self.b, self.comm
+        for s, b in zip(S, B):
+            s.plane_out(RHO_ROW0, b["rho_send"])
+            s.plane_out(PHI_LAST, b["pb_send"])
+        C.shift_up([b["rho_send"] for b in B], [b["rho_recv"] for b in B])
+        C.shift_down([b["pb_send"] for b in B], [b["pb_recv"] for b in B])
+        rows = []
+        for s, b in zip(S, B):
+            if not s.last:
+                s.plane_in(RHO_HALO, b["rho_recv"])
+            rows.append(torch.zeros(16, dtype=torch.float64, device=b["sums"].device))
+            s.report_partial(b["pb_recv"] if s.rank > 0 else None, rows[-1])
+        allrows = C.allgather(rows)[0]                       # [nranks, 16] in slab order
+        s0 = S[0]
+        return report_from_sums(fold_report_rows(allrows.cpu().numpy()), s0.T_total * s0.nx * s0.ny)
 
     def iterate(self, n, tau, sigma, eps, k, check_every=8):
         """Up to n outer iterations; stops when the device control block says done (checked every
