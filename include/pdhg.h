@@ -183,7 +183,10 @@ int pdhg_device_bytes(pdhg_ctx* ctx, unsigned long long* bytes);
  * nx = 512 ... 8192: k_precond_xt_f64_2d; PDHG_XT64=0 the generic kernel), "xt64_dma" 1/0 (its nx = 4096
  * column-pair form on single contexts with the forward rows staged by LDS DMA and b' in registers; PDHG_XT64_DMA=0
  * off; "xt64_bpr" 1/0: b' in registers, PDHG_XT64_BPR), "ip_rows" 1/0 (fp64 ny = 8192: row pairs in
- * one padded line), "upd8192" 1/0 (fp64 ny = 8192 with half-real x blocks: the 2-row fast update), "tc_spec" 1/0
+ * one padded line), "upd8192" 1/0 (fp64 ny = 8192 with half-real x blocks: the 2-row fast update), "upd64_pair" 1/0
+ * (fp64 ny = 2048 / 4096 on single contexts with nx % 8 == 0: the update on pairs of 4-row tasks,
+ * k_invy_update_pair_2d, phi' and phi_bar bitwise the 4-row kernel's; default on windows of >= 100 rows, PDHG_UPD_PAIR=1 / 0 forces it on / off), "upd_grid" (workgroups
+ * of the fast update kernels as launched; PDHG_UPD_GRID caps the fp64 4-row / 8-row ones, tests), "tc_spec" 1/0
  * (fp64 C3 shape, windows of >= 100 rows: the residual spectrum in task order), "t1_xt64" 1/0 (fp64 one-row windows at a power-of-two nx in
  * 512..4096: the carry-free k_precond_x_t1_2d<..., double>; PDHG_T1_XT=0 off), "graph" 1/0 (pdhg_iterate replays
  * windows of iterations from a captured HIP graph; default on, environment PDHG_GRAPH=0 launches every

@@ -773,6 +773,18 @@ struct Impl : ImplBase {
           if (pp.upd_t1 == 2) return launch(k_invy_update_fast_2d<2048, 4, 256, 2, double, true>, gf, dim3(256), lds, p, twy);
           return launch(k_invy_update_fast_2d<2048, 4, 256, 4, double, true>, gf, dim3(256), lds, p, twy);
         }
+        if (pp.upd64_pair) {   // pairs of x-adjacent 4-row tasks (grid and partial rows: the pair count's)
+          auto go = [&](auto PFc) {
+            constexpr int PF_ = decltype(PFc)::value;
+            if (pb.ny == 4096) return launch(k_invy_update_pair_2d<4096, 512, PF_>, gf, dim3(512), pp.lds_upd64, p, twy);
+            return launch(k_invy_update_pair_2d<2048, 512, PF_>, gf, dim3(512), pp.lds_upd64, p, twy);
+          };
+          switch (pp.upd_pair_pf) {
+            case 2: return go(IC<2>{});
+            case 3: return go(IC<3>{});
+            default: return go(IC<4>{});
+          }
+        }
         if (pb.ny == 4096) return launch(k_invy_update_fast_2d<4096, 4, 512, 4, double>, gf, dim3(512), pp.lds_upd64, p, twy);
         return launch(k_invy_update_fast_2d<2048, 4, 512, 4, double>, gf, dim3(512), pp.lds_upd64, p, twy);
       }

@@ -849,6 +849,147 @@ __global__ void __launch_bounds__(NT) k_invy_update_fast_2d(KP<R> p, const cplx<
   }
   block_reduce_store<3>(s, p.partials, blockIdx.x);
 }
+// k_invy_update_fast_2d<N, 4, NT, PF, double> on pairs of x-adjacent 4-row tasks (rows x0 .. x0+7 of one time row;
+// nx % 8 == 0, B = 2 .. 16, single contexts: path_plan.hpp upd64_pair).  The pair's spectrum is one batch of
+// 8 N / 4 / NT 32-B pieces per thread: a column block holds 2 B pieces of the pair, the first B the first task's, and
+// consecutive lanes take consecutive pieces, so the batch reads whole 128-B lines where the 4-row task reads 64 B of
+// each (B = 2).  Odd loads flip bit lB of the lane's piece index, so every thread ends with as many pieces of either
+// task; the addresses of a wave instruction are the same set.  The first task's pieces go to LDS and run as in the
+// 4-row kernel; the second task's stay in registers across that and feed its transform with no load and no wait
+// (its first old-phi rows are issued before they are written to LDS).  Every output element is computed as the
+// 4-row kernel computes it (same values in the same LDS positions, the same transform and update text); the sums
+// of a workgroup cover other tasks, so the err sums differ from the 4-row form's in summation order only.
+// grid: G workgroups striding over the T * nx/8 pairs; block NT; LDS as the 4-row kernel.
+template <int N, int NT, int PF>
+__global__ void __launch_bounds__(NT) k_invy_update_pair_2d(KP<double> p, const cplx<double>* __restrict__ twy) {
+  using R = double;
+  using C = cplx<R>;
+  using V = V4<R>;
+  constexpr int RW = 4, NL = RW / 2;
+  constexpr int GPT = (N / 4) / NT;
+  if (p.ctrl->done) return;
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  C* A = reinterpret_cast<C*>(smem_raw);
+  R* Af = reinterpret_cast<R*>(A);
+  C* twl = A + NL * Pad<N>::LINE;
+  fill_twlds<C, N>(twl, twy, 1, TwLds<N>::SIZE);
+  const int nx = p.nx, B = p.B, nb = p.nb;
+  const int npx = nx / (2 * RW);
+  const int npair = npx * p.T;
+  const size_t plane = (size_t)nx * N;
+  const R scale = p.tau * p.inv_n;
+  const int lB = p.lB;
+  const int lCS = lB + 1;   // log2 of the pair's 2 B pieces per column block
+  const int tid = threadIdx.x;
+  constexpr int NLD = 2 * RW * N / 4 / NT, NH = NLD / 2;
+  static_assert((2 * RW * N / 4) % NT == 0 && NLD % 2 == 0 && NLD <= 16 && NT % 32 == 0, "one batch, halved per task");
+  double s[3] = {0.0, 0.0, 0.0};
+  for (int pr = xcd_remap(blockIdx.x, gridDim.x); pr < npair; pr += gridDim.x) {
+    const int j = pr / npx;
+    int x0 = (pr - j * npx) * (2 * RW);
+    const R* wk = p.work + (size_t)j * nb * nx * B;
+    int tl = tid;
+    asm volatile("" : "+v"(tl));
+    const int hi = (tl >> lB) & 1;   // the lane's even loads are the second task's
+    V cur[NH], held[NH];
+    {
+      V v[NLD];
+#pragma unroll
+      for (int i = 0; i < NLD; ++i) {
+        const int t = (tl ^ ((i & 1) << lB)) + i * NT;
+        v[i] = ld4(wk + ((size_t)(t >> lCS) * nx + x0) * B + (t & (2 * B - 1)) * 4);
+      }
+#pragma unroll
+      for (int k = 0; k < NH; ++k) {
+        cur[k] = hi ? v[2 * k + 1] : v[2 * k];
+        held[k] = hi ? v[2 * k] : v[2 * k + 1];
+      }
+    }
+    // piece k of a task came with load 2 k + odd: column block (tl >> lCS) + (2 k + odd) NT / 2B, part tl & (B - 1)
+    auto put = [&](const V (&w)[NH], int odd) {
+#pragma unroll
+      for (int k = 0; k < NH; ++k) {
+        const int b = (tl >> lCS) + (2 * k + odd) * (NT >> lCS), part = tl & (B - 1);
+        if (B == 2) {   // rows r, r+1 (r = 2 part) at columns 2b, 2b+1: two complex elements
+          C* Al = A + part * Pad<N>::LINE;
+          Al[pix(2 * b)] = cmk<C>(w[k].x, w[k].z);
+          Al[pix(2 * b + 1)] = cmk<C>(w[k].y, w[k].w);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const int f = part * 4 + e;
+            const int r = f >> lB, c = f & (B - 1);
+            Af[((r >> 1) * Pad<N>::LINE + pix(b * B + c)) * 2 + (r & 1)] = f4(w[k], e);
+          }
+        }
+      }
+    };
+    R* phi = p.phi + (size_t)(j + 1) * plane;
+    R* pbar = p.phibar + (size_t)(j + 1) * plane;
+#pragma unroll 1
+    for (int half = 0; half < 2; ++half, x0 += RW) {
+      constexpr int NS = GPT * NL;
+      V op[NS][2];
+      auto ldstep = [&](int s) {
+        const size_t idx = (size_t)(x0 + 2 * (s % NL)) * N + 4 * (tid + (s / NL) * NT);
+        op[s][0] = ld4(phi + idx);
+        op[s][1] = ld4(phi + idx + N);
+      };
+      ldstep(0);
+      put(cur, half ? 1 - hi : hi);
+      lds_sync();
+      if (!(p.dbg & 64)) lds_fft_inplace_tl<C, N, NL, NT, Pad<N>::LINE>(A, twl);   // PDHG_DBG 64: timing only
+#pragma unroll
+      for (int s = 1; s < PF && s < NS; ++s) ldstep(s);
+#pragma unroll
+      for (int gi = 0; gi < GPT; ++gi) {
+        const int y = 4 * (tid + gi * NT);
+#pragma unroll
+        for (int l = 0; l < NL; ++l) {   // rows 2l (real part) and 2l+1 (imaginary part) of line l
+          const int st = gi * NL + l;
+          const V o4[2] = {op[st][0], op[st][1]};
+          if (st + PF < NS) ldstep(st + PF);
+          const C* Z = A + l * Pad<N>::LINE;
+          V u[2];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            R a, b2;
+            hartley_padded<C, R>(Z, N, y + e, a, b2);
+            f4set(u[0], e, a);
+            f4set(u[1], e, b2);
+          }
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const int xr = x0 + 2 * l + h;
+            if (xr < p.xl0 || xr >= p.xl1) continue;   // (never on the contexts that select this kernel)
+            const size_t idx = (size_t)xr * N + y;
+            V nw, pb;
+            R fs[3] = {(R)0, (R)0, (R)0};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+              const R o = f4(o4[h], e);
+              const R n = o + scale * f4(u[h], e);
+              f4set(nw, e, n);
+              f4set(pb, e, (R)2 * n - o);
+              const R d = n - o;
+              fs[0] = fmar(d, d, fs[0]);
+              fs[1] = fmar(o, o, fs[1]);
+              fs[2] = fmar(n, n, fs[2]);
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) s[i] += (double)fs[i];
+            st4(phi + idx, nw);
+            st4(pbar + idx, pb);
+          }
+        }
+      }
+      lds_sync();
+#pragma unroll
+      for (int k = 0; k < NH; ++k) cur[k] = held[k];
+    }
+  }
+  block_reduce_store<3>(s, p.partials, blockIdx.x);
+}
 template <int N, int RW, int NT, int PF = 1>
 __global__ void __launch_bounds__(NT) k_invy_update_fast_mixed_2d(KP<float> p, const float2* __restrict__ twy,
                                                                   PhiX<float, double> px) {

@@ -96,6 +96,8 @@ struct PathPlan {
   bool res64 = false;             // fp64 residual and update through the fast row kernels (4-row groups)
   bool ip_rows = false;           // fp64 ny = 8192: generic row kernels on one padded in-place line (FFTIp)
   bool upd8192 = false;           // fp64 ny = 8192, half-real x: update through the fast row kernel on 2-row tasks
+  bool upd64_pair = false;        // fp64 ny = 2048 / 4096: update on 8-row task pairs (k_invy_update_pair_2d)
+  int upd_pair_pf = 4;            // ... its old-phi row pairs in flight (2..4)
   bool tc_spec = false;           // fp64 C3: residual spectrum in task order (KP::rspec)
   bool to_c4 = false;             // C4 (half-real x blocks): fused residual in task order + transpose
   int res_threads = 0, upd_threads = 0;   // as launched: fast row kernels' threads after half_nt (0: not the fast rows)
@@ -336,6 +338,20 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
         // the update through the fast row kernel too: + the twiddle-seed table (152 KiB at ny = 4096)
         pl.lds_upd64 = pl.lds_res64 + (size_t)twlds_size(ny) * csz;
         pl.g_fast_upd = std::min((nx / 4) * T, 2048);
+        // the update on pairs of x-adjacent 4-row tasks (k_invy_update_pair_2d: whole 128-B spectrum lines, the second
+        // task's half held in registers across the first; bitwise the 4-row kernel's phi' / phi_bar): single contexts
+        // with an even task count per time row, whole column blocks of 2 .. 16 columns.  One-row windows at ny = 2048
+        // keep their 256-thread forms (upd_t1), x-slabs (ghost rows) and t-slabs the 4-row kernel.  C3 fp64
+        // headline, alternating with the parent: update 21.73 - 21.86 -> 20.35 - 20.58 ms, step 115.34 -> 114.07 ms
+        // (profiles/headline_upd64_pair.txt).  Interleaved A/B: c3w100 update 10.75 -> 10.47 ms, c3w25 2.753 -> 2.791
+        // (a loss), so by default windows of >= 100 rows only; PDHG_UPD_PAIR=1 any window, =0 the 4-row kernel
+        // (reads B, upd_t1)
+        const bool pair_ok = !slab && !xslab && (nx / 4) % 2 == 0 && T >= 1 && B >= 2 && B <= 16 && ny % B == 0 &&
+                             !(ny == 2048 && pl.upd_t1 > 0);
+        pl.upd64_pair = pair_ok && (tn.upd_pair ? *tn.upd_pair != 0 : T >= 100);
+        pl.upd_pair_pf = tn.upd_pair_pf;
+        if (pl.upd64_pair) pl.g_fast_upd = std::min((nx / 8) * T, 2048);
+        if (tn.upd_grid) pl.g_fast_upd = std::min(pl.g_fast_upd, *tn.upd_grid);
       }
     }
     // fp64 C3 shape: the residual spectrum handed to the x transform in task order (p.rspec; one contiguous run per
@@ -494,6 +510,8 @@ inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const st
   else if (k == "glb_line") *value = pl.glb_line ? 1 : 0;
   else if (k == "ip_rows") *value = pl.ip_rows ? 1 : 0;   // fp64 ny = 8192 row pairs in one padded line
   else if (k == "upd8192") *value = pl.upd8192 ? 1 : 0;   // fp64 ny = 8192: 2-row fast update
+  else if (k == "upd64_pair") *value = pl.upd64_pair ? 1 : 0;   // fp64 ny = 2048 / 4096: update on 8-row task pairs
+  else if (k == "upd_grid") *value = pl.g_fast_upd;   // workgroups of the fast update kernels
   else if (k == "tc_spec") *value = pl.tc_spec ? 1 : 0;   // fp64 C3: task-order residual spectrum
   else if (k == "to_c4") *value = pl.to_c4 ? 1 : 0;       // C4: task-order residual spectrum + transpose
   else if (k == "thomas_chunk") *value = pl.thomas_chunk ? 1 : 0;

@@ -44,6 +44,9 @@ struct Tuning {
   EnvInt upd_t1;           // PDHG_UPD_T1: fp64 ny = 2048 update on one-row windows (0: 512 threads, 1: PF 4, 2: PF 2)
   EnvInt res64_nt2048;     // PDHG_RES64_NT2048: fp64 unfused residual threads at ny = 2048 (256 / 512; A/B)
   EnvInt upd8192;          // PDHG_UPD8192=0: fp64 ny = 8192 update through the generic kernel (A/B)
+  EnvInt upd_pair;         // PDHG_UPD_PAIR: fp64 ny = 2048 / 4096 update on 8-row task pairs (k_invy_update_pair_2d; default: T >= 100)
+  int upd_pair_pf = 4;     // PDHG_UPD_PAIR_PF: ... its old-phi row pairs in flight (2..4)
+  EnvInt upd_grid;         // PDHG_UPD_GRID: at most this many workgroups in the fp64 4-row / 8-row update (tests)
   int rows_var = 0;        // PDHG_ROWS_VAR=1: fp32 ny = 2048 / 4096 rows as 4 rows per block (measured loser)
   int half_nt = 3;         // PDHG_HALF_NT: ny = 4096 rows with 512 threads (bit 0 fused residual, bit 1 update)
   // PDHG_RES64_NT=1024: fp64 fused residual threads at ny = 4096 (GPT = 1, 128 VGPRs + 108 B of spills; interleaved
@@ -115,6 +118,9 @@ struct Tuning {
     t.upd_t1 = env_int("PDHG_UPD_T1");
     if ((t.res64_nt2048 = env_int("PDHG_RES64_NT2048"))) t.res64_nt2048 = *t.res64_nt2048 == 256 ? 256 : 512;
     t.upd8192 = env_int("PDHG_UPD8192");
+    t.upd_pair = env_int("PDHG_UPD_PAIR");
+    t.upd_pair_pf = std::max(2, std::min(4, env_int("PDHG_UPD_PAIR_PF", t.upd_pair_pf)));
+    if ((t.upd_grid = env_int("PDHG_UPD_GRID"))) t.upd_grid = std::max(1, *t.upd_grid);
     t.rows_var = env_int("PDHG_ROWS_VAR", t.rows_var);
     t.half_nt = env_int("PDHG_HALF_NT", t.half_nt);
     t.res64_nt = env_int("PDHG_RES64_NT", t.res64_nt) == 1024 ? 1024 : 512;
