@@ -330,8 +330,10 @@ __global__ void __launch_bounds__(512) k_precond_xt_2d(KP<R> p, F plx, const cpl
 // sums: [0] sum (phi'-phi)^2, [1] sum phi^2 (old), [2] sum phi'^2 (NaN detector)
 // invy_update_2d_body<.., P>: k_invy_update_2d (below) with phi / phi_bar in P, for the mixed context's
 // k_invy_update_mixed_2d: U in float out of the transform, phi' = phi + (double)(tau / n) (double)U, phi_bar and the
-// sums in double.  The fp32 / fp64 kernel keeps its own text: routed through this body its code came out differently
-// scheduled and contracted (states off in the last bit), and those results must not move.
+// sums in double.  The fp32 / fp64 kernel keeps its own text: routed through this body (P = R, phi' = old + scale * u
+// without casts) all 22 instantiations differ from it in opcode counts -- the body's block-size read and KP reads
+// (DESIGN.md "Mixed precision"), e.g. FFTFx<256>: 4 s_load_dword for 10, 5 global_load_ushort, 3 v_add_f32 for 5 --
+// and those results must not move.
 template <typename R, class F, typename P = R>
 __device__ __forceinline__ void invy_update_2d_body(const KP<R>& p, const PhiX<R, P>& px, F ply,
                                                     const cplx<R>* __restrict__ twy) {
@@ -570,7 +572,9 @@ __device__ __forceinline__ R dual_point_x(const KP<R>& p, const PhiX<R, P>& px, 
 // sums: [0] sum (rho'-rho)^2 [1] sum rho'^2 [2] sum rho^2, then per live alpha array a:
 //       [3+3a] sum (alp'-alp)^2 [4+3a] sum alp'^2 [5+3a] sum alp^2
 // dual_2d_body<.., P>: k_dual_2d (below) with phi_bar in P, for the mixed context's k_dual_mixed_2d (float state,
-// double phi_bar); the fp32 / fp64 kernel keeps its own text (see invy_update_2d_body)
+// double phi_bar); the fp32 / fp64 kernel keeps its own text: as a wrapper around this body its 6 instantiations keep
+// their registers and LDS but take the body's block-size read (a global_load_ushort for an s_load_dword, one more
+// s_cmp_eq_u32; see invy_update_2d_body)
 template <typename R, int EGNO, typename P = R>
 __device__ __forceinline__ void dual_2d_body(const KP<R>& p, const PhiX<R, P>& px) {
   if (p.ctrl->done || p.ctrl->inner_done) return;

@@ -564,7 +564,10 @@ __global__ void __launch_bounds__(256) k_res_fwdy_fused_transpose_2d(KP<R> p, in
 // invy_update_fast_body<.., P>: k_invy_update_fast_2d (below) with phi / phi_bar in P, for the mixed context's
 // k_invy_update_fast_mixed_2d: the spectrum, the transform and U in float, the old-phi rows prefetched as doubles
 // (32-B dbl4 accesses), phi' = phi + (double)(tau / n) (double)U, phi_bar and the sums of the 4 points in double.
-// The fp32 / fp64 kernel keeps its own text, so its code and results stay the parent's bit for bit.
+// The fp32 / fp64 kernel keeps its own text: as a wrapper around this body with P = R, and likewise with only the
+// per-task tail (ldstep(0) .. the closing lds_sync) shared with k_invy_update_pair_2d, every instantiation's code
+// differed from its own text's in opcode counts (DESIGN.md "Mixed precision": the block-size read and the KP reads
+// of a body that is simplified before it is inlined; scripts/isa_compare.py, profiles/one_text_isa.txt).
 template <int N, int RW, int NT, int PF, typename R, bool G16, typename P = R>
 __device__ __forceinline__ void invy_update_fast_body(const KP<R>& p, const PhiX<R, P>& px,
                                                       const cplx<R>* __restrict__ twy) {
@@ -1569,7 +1572,9 @@ __global__ void __launch_bounds__(512) k_precond_xt_ws_2d(KP<float> p, const flo
 // dual_fast_body<.., P>: k_dual_fast_2d (below) with phi_bar in P, for the mixed context's k_dual_fast_mixed_2d: the
 // centre, the x neighbours, the wave-edge y neighbours and row j loaded as doubles, the y neighbours crossing lanes as
 // doubles, the phi_bar terms of a point in double and rounded to float once (dual_point_x), rho / alp and the sums as
-// in fp32.  The fp32 / fp64 kernel keeps its own text (as k_invy_update_fast_2d).
+// in fp32.  The fp32 / fp64 kernel keeps its own text: tried as a wrapper around this body (dual_point_x is dual_point
+// for P == R), all 15 instantiations came out with the body's block-size read (one more s_cmp_lt_u32 / s_cselect, a
+// global_load_ushort for an s_load_dword) and fp32 egno 1 / 2 with 4 - 10 more VGPRs (DESIGN.md "Mixed precision").
 template <int EGNO, typename R, int ONE, typename P = R>
 __device__ __forceinline__ void dual_fast_body(const KP<R>& p, const PhiX<R, P>& px, int jchunk, int jbase, int jend,
                                                int zbase) {

@@ -40,7 +40,9 @@ constexpr int kDualMultiMax = 10;   // rho_alp_iters handled in registers (the r
 
 // dual_multi_body<.., P>: k_dual_multi_2d (below) with phi_bar in P, for the mixed context's k_dual_multi_mixed_2d:
 // phi_bar loaded as doubles, dual_pre<double> on the PhiX reciprocals rounded to float once per point and pass,
-// dual_core<float>.  The fp32 / fp64 kernel keeps its own text (its code and results stay bit for bit).
+// dual_core<float>.  The fp32 / fp64 kernel keeps its own text: as a wrapper around this body (dual_pre<R>(p, ..) for
+// P == R) its 12 instantiations allocate and contract differently (fp64 egno 1 final pass 235 -> 203 VGPRs, fp32 egno 3
+// final pass 160 v_mul_f32 for 169; DESIGN.md "Mixed precision"), so its results would move.
 template <int EGNO, typename R, int NSUB, bool FINAL, typename P = R>
 __device__ __forceinline__ void dual_multi_body(const KP<R>& p, const PhiX<R, P>& px, int slo, int kmax,
                                                 int table_rows, int jchunk, int jbase, int jend, int zbase, int xrun) {
