@@ -192,7 +192,28 @@ int pdhg_device_bytes(pdhg_ctx* ctx, unsigned long long* bytes);
  * windows of iterations from a captured HIP graph; default on, environment PDHG_GRAPH=0 launches every
  * iteration eagerly), "graph_window" (iterations per replayed graph), "mixed" 1/0 (precision 12: fp32 state with
  * fp64 phi / phi_bar; the other keys then answer for the fp32 kernels chosen -- "fast_dual" 0 and "fused_residual" 0
- * always, the dual being the row-per-thread sweep or the generic per-point kernel -- and "dual64" is 0). */
+ * always, the dual being the row-per-thread sweep or the generic per-point kernel -- and "dual64" is 0).
+ *
+ * The kernel each 2-D stage launches (the launchers switch on exactly these; 1-D contexts answer 0): "<stage>_kernel"
+ * is the family code below, "<stage>_shape" the threads per workgroup as launched, and "<stage>_n", "<stage>_a",
+ * "<stage>_b", "<stage>_c" the family's template integers (line length; lines or rows per workgroup / ONE / RX; thread
+ * bound, RB or YPL; PF, RPRE or the fp64 x kernel's BPR 1 | TC 2 | DMA 4 flags; 0 where unused), for the stages
+ *   "xt" (x transform of a window): 1 single-role k_precond_xt_fast_2d, 2 warp-specialised k_precond_xt_ws_2d,
+ *     3 row-batched k_precond_xt_batch_2d, 4 k_precond_xt_dma_2d, 5 its half-real form (1 .. 5 are "fast_xt"'s codes),
+ *     6 fp64 k_precond_xt_f64_2d, 7 the generic runtime-radix k_precond_xt_2d;
+ *   "xt_one_row" (T = 1 windows of single and x-slab contexts; 0: the window kernel runs): k_precond_x_t1_2d in
+ *     8 fp32, 9 fp64, 10 fp64 with the G16 twiddle seeds;
+ *   "res" (residual without the fused sweep) and "res_fused" (0: none; the kernel that completes the rows the fused dual
+ *     sweep formed): 1 generic k_res_fwdy_2d, 2 fp32 k_res_fwdy_fast_2d, 3 its fp64 4-row form, 4 fp32
+ *     k_res_fwdy_fused_2d, 5 its fp64 form;
+ *   "upd": 1 generic k_invy_update_2d, 2 k_invy_update_mixed_2d, 3 fp32 k_invy_update_fast_2d, 4 k_invy_update_fast_mixed_2d,
+ *     5 the fp64 4-row k_invy_update_fast_2d, 6 its one-row form with G16 seeds, 7 k_invy_update_pair_2d, 8 the 2-row
+ *     tasks at ny = 8192;
+ *   "dual" and "dual_fused" (0: none; the sweep that also forms the next residual): 1 per-point k_dual_2d,
+ *     2 k_dual_mixed_2d, 3 row-per-thread k_dual_fast_2d, 4 k_dual_fast_mixed_2d, 5 k_dual_lds_2d, 6 its FR form.
+ * The older "as launched" keys ("fast_xt", "t1_xt64", "t1_g16", "xt64_dma", "xt64_bpr", "rows_rw", "res_threads",
+ * "upd_threads", "res64_nt", "upd_t1", "upd64_pair", "upd8192", "fast_dual", "dual_ypl", "dual_one") are read off the
+ * same choices.  New keys do not change PDHG_ABI_VERSION (no struct, no signature). */
 int pdhg_path_info(pdhg_ctx* ctx, const char* key, int* value);
 /* The same keys for the single context pdhg_create would build from `prob` under the current environment, without a
  * device: the problem is validated as in pdhg_create (same status codes) and the kernel paths are planned, nothing is

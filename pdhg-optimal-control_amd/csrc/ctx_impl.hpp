@@ -476,25 +476,16 @@ struct Impl : ImplBase {
     }
     return fn(FFTRt{pl, 1});
   }
-  // fast row-kernel dispatch on ny (compile-time N, RW, NT)
-  template <typename Fn>
-  int with_fast_rows(Fn&& fn) {
-    if constexpr (sizeof(R) == 4) {
-      switch (pb.ny) {
-        case 256: return fn(IC<256>{}, IC<8>{}, IC<64>{});
-        case 512: return fn(IC<512>{}, IC<8>{}, IC<128>{});
-        case 1024: return fn(IC<1024>{}, IC<8>{}, IC<256>{});
-        case 2048:
-          if (pp.rows_var == 1) return fn(IC<2048>{}, IC<4>{}, IC<256>{});
-          return fn(IC<2048>{}, IC<8>{}, IC<512>{});
-        case 4096:
-          if (pp.rows_var == 1) return fn(IC<4096>{}, IC<4>{}, IC<512>{});
-          return fn(IC<4096>{}, IC<8>{}, IC<1024>{});
-        case 8192: return fn(IC<8192>{}, IC<4>{}, IC<1024>{});
-        default: break;
-      }
-    }
-    return fail(PDHG_ERR_UNSUPPORTED, "no fast row kernel for ny=%d", pb.ny);
+  // a KernelChoice as one switch value: every launcher below has one case, with one launch line, per instantiation
+  static constexpr unsigned long long ck(int family, int n = 0, int a = 0, int b = 0, int c = 0) {
+    using U = unsigned long long;
+    return ((U)family << 56) | ((U)n << 40) | ((U)a << 28) | ((U)b << 14) | (U)c;
+  }
+  static unsigned long long ck(const KernelChoice& k) { return ck(k.family, k.n, k.a, k.b, k.c); }
+  // a (family, shape) the stage's switch does not know is an error, never another kernel
+  int no_kernel(const char* stage, const KernelChoice& k) {
+    return fail(PDHG_ERR_STATE, "%s: no kernel for family %d with shape (%d, %d, %d, %d), %d threads", stage, k.family,
+                k.n, k.a, k.b, k.c, k.threads);
   }
 
   template <typename Fn>
@@ -539,37 +530,28 @@ struct Impl : ImplBase {
   // the fused residual kernel over time rows [lo, hi) (launch_residual's fused branch); persistent grids, one
   // workgroup per CU (LDS)
   int launch_fused_residual(const KP<R>& p, int lo, int hi) {
-    const int rows = hi - lo;
-    if constexpr (sizeof(R) == 8) {
-      return with_egno<2>([&](auto eg) {
-        constexpr int E = decltype(eg)::value;
-        if (pb.ny == 8192)   // quarter-tile tasks: one padded line of 8192 complex doubles (+ the strip-edge terms)
-          return launch(k_res_fwdy_fused_2d<E, 8192, 2, 512, double>, dim3(std::min((pb.nx / 2) * rows, n_cu)),
-                        dim3(512), (size_t)Pad<8192>::LINE * sizeof(C), p, twy);
-        const dim3 g(std::min((pb.nx / 4) * rows, n_cu));
-        if (pb.ny != 4096)
-          return launch(k_res_fwdy_fused_2d<E, 2048, 4, 512, double>, g, dim3(512), pp.lds_upd64, p, twy);
-        if (pp.res64_nt == 1024)   // A/B: 16 waves per CU (GPT = 1)
-          return launch(k_res_fwdy_fused_2d<E, 4096, 4, 1024, double>, g, dim3(1024), pp.lds_upd64, p, twy);
-        return launch(k_res_fwdy_fused_2d<E, 4096, 4, 512, double>, g, dim3(512), pp.lds_upd64, p, twy);
-      });
-    } else {
-      return with_fast_rows([&](auto Nc, auto RWc, auto NTc) {
-        constexpr int N_ = decltype(Nc)::value, RW_ = decltype(RWc)::value, NT_ = decltype(NTc)::value;
-        if constexpr ((RW_ == 8 || (RW_ == 4 && N_ == 8192)) && N_ % 256 == 0 && (N_ / 4) % NT_ == 0) {
-          const dim3 g(std::min((pb.nx / RW_) * rows, n_cu));
-          return with_egno<2>([&](auto eg) {
-            constexpr int E = decltype(eg)::value;
-            if constexpr (NT_ == 1024) {
-              if (pp.res_threads == 512)
-                return launch(k_res_fwdy_fused_2d<E, N_, RW_, 512>, g, dim3(512), pp.lds_fast_tw, p, twy);
-            }
-            return launch(k_res_fwdy_fused_2d<E, N_, RW_, NT_>, g, dim3(NT_), pp.lds_fast_tw, p, twy);
-          });
-        }
-        return fail(PDHG_ERR_STATE, "fused residual without 8-row fast kernels (ny=%d)", pb.ny);
-      });
-    }
+    const KernelChoice& k = pp.res_fused;
+    const dim3 g(std::min((pb.nx / std::max(k.a, 1)) * (hi - lo), n_cu));
+    return with_egno<2>([&](auto eg) {
+      constexpr int E = decltype(eg)::value;
+      auto go = [&](auto kern) { return launch(kern, g, dim3(k.threads), k.lds, p, twy); };
+      if constexpr (sizeof(R) == 4) switch (ck(k)) {
+        case ck(RES_FUSED, 256, 8, 64): return go(k_res_fwdy_fused_2d<E, 256, 8, 64>);
+        case ck(RES_FUSED, 512, 8, 128): return go(k_res_fwdy_fused_2d<E, 512, 8, 128>);
+        case ck(RES_FUSED, 1024, 8, 256): return go(k_res_fwdy_fused_2d<E, 1024, 8, 256>);
+        case ck(RES_FUSED, 2048, 8, 512): return go(k_res_fwdy_fused_2d<E, 2048, 8, 512>);
+        case ck(RES_FUSED, 4096, 8, 1024): return go(k_res_fwdy_fused_2d<E, 4096, 8, 1024>);
+        case ck(RES_FUSED, 4096, 8, 512): return go(k_res_fwdy_fused_2d<E, 4096, 8, 512>);
+        case ck(RES_FUSED, 8192, 4, 1024): return go(k_res_fwdy_fused_2d<E, 8192, 4, 1024>);
+        case ck(RES_FUSED, 8192, 4, 512): return go(k_res_fwdy_fused_2d<E, 8192, 4, 512>);
+      } else switch (ck(k)) {
+        case ck(RES_FUSED64, 8192, 2, 512): return go(k_res_fwdy_fused_2d<E, 8192, 2, 512, double>);
+        case ck(RES_FUSED64, 2048, 4, 512): return go(k_res_fwdy_fused_2d<E, 2048, 4, 512, double>);
+        case ck(RES_FUSED64, 4096, 4, 512): return go(k_res_fwdy_fused_2d<E, 4096, 4, 512, double>);
+        case ck(RES_FUSED64, 4096, 4, 1024): return go(k_res_fwdy_fused_2d<E, 4096, 4, 1024, double>);
+      }
+      return no_kernel("res_fused", k);
+    });
   }
 
   // C4's task-order residual spectrum (p.rspec) of time rows [lo, hi) into the blocked layout of `work`
@@ -585,8 +567,9 @@ struct Impl : ImplBase {
   // whole window (lo = 0, hi = T).
   int launch_residual(KP<R> p, int lo, int hi) {
     if (hi <= lo) return PDHG_OK;
-    const bool fused = pp.fuse_res && res_valid && (slab || (lo == 0 && hi == pb.T));
-    if (!fused && !pp.fast_rows && !(sizeof(R) == 8 && pp.res64) && (lo != 0 || hi != pb.T))
+    const KernelChoice& k = pp.res;
+    const bool fused = pp.res_fused.family && res_valid && (slab || (lo == 0 && hi == pb.T));
+    if (!fused && k.family == RES_GENERIC && (lo != 0 || hi != pb.T))
       return fail(PDHG_ERR_UNSUPPORTED, "row-range residual needs the fast row kernels");
     ProfScope ps(this, "residual");
     p.row_base = lo;
@@ -602,37 +585,32 @@ struct Impl : ImplBase {
       if (int rc = launch_fused_residual(p, lo, hi)) return rc;
       return pp.to_c4 ? launch_spec_to_blocked(p, lo, hi) : (int)PDHG_OK;
     }
-    if constexpr (sizeof(R) == 8) {
-      if (pp.res64)   // 1024 threads cap the fp64 rows at 128 VGPRs (spills); ny = 2048 A/B: 256 threads (2 per CU)
-        return with_egno<3>([&](auto eg) {
-          constexpr int E = decltype(eg)::value;
-          const dim3 g((pb.nx / 4) * (hi - lo));
-          if (pb.ny == 4096)
-            return launch(k_res_fwdy_fast_2d<E, 4096, 4, 512, double>, g, dim3(512), pp.lds_res64, p, twy);
-          if (pp.res64_nt2048 == 256)
-            return launch(k_res_fwdy_fast_2d<E, 2048, 4, 256, double>, g, dim3(256), pp.lds_res64, p, twy);
-          return launch(k_res_fwdy_fast_2d<E, 2048, 4, 512, double>, g, dim3(512), pp.lds_res64, p, twy);
+    return with_egno<3>([&](auto eg) {
+      constexpr int E = decltype(eg)::value;
+      if (k.family == RES_GENERIC)
+        return with_line_fft(pp.ply, [&](auto f) {
+          using F = decltype(f);
+          if (k.b == 256) return launch(k_res_fwdy_2d<R, E, F, 256>, dim3(pp.gx1), dim3(k.threads), k.lds, p, f, twy);
+          return launch(k_res_fwdy_2d<R, E, F, 1024>, dim3(pp.gx1), dim3(k.threads), k.lds, p, f, twy);
         });
-    }
-    if (pp.fast_rows)
-      return with_fast_rows([&](auto Nc, auto RWc, auto NTc) {
-        constexpr int N_ = decltype(Nc)::value, RW_ = decltype(RWc)::value, NT_ = decltype(NTc)::value;
-        return with_egno<3>([&](auto eg) {
-          constexpr int E = decltype(eg)::value;
-          if constexpr (sizeof(R) == 4)
-            return launch(k_res_fwdy_fast_2d<E, N_, RW_, NT_>, dim3((pb.nx / RW_) * (hi - lo)), dim3(NT_), pp.lds_fast,
-                          p, twy);
-          return (int)PDHG_OK;
-        });
-      });
-    return with_line_fft(pp.ply, [&](auto f) {
-      using F = decltype(f);
-      return with_egno<3>([&](auto eg) {
-        constexpr int E = decltype(eg)::value;
-        if (pp.nt_row <= 256)
-          return launch(k_res_fwdy_2d<R, E, F, 256>, dim3(pp.gx1), dim3(pp.nt_row), pp.lds_res, p, f, twy);
-        return launch(k_res_fwdy_2d<R, E, F, 1024>, dim3(pp.gx1), dim3(pp.nt_row), pp.lds_res, p, f, twy);
-      });
+      auto go = [&](auto kern) {
+        return launch(kern, dim3((pb.nx / std::max(k.a, 1)) * (hi - lo)), dim3(k.threads), k.lds, p, twy);
+      };
+      if constexpr (sizeof(R) == 4) switch (ck(k)) {
+        case ck(RES_FAST, 256, 8, 64): return go(k_res_fwdy_fast_2d<E, 256, 8, 64>);
+        case ck(RES_FAST, 512, 8, 128): return go(k_res_fwdy_fast_2d<E, 512, 8, 128>);
+        case ck(RES_FAST, 1024, 8, 256): return go(k_res_fwdy_fast_2d<E, 1024, 8, 256>);
+        case ck(RES_FAST, 2048, 8, 512): return go(k_res_fwdy_fast_2d<E, 2048, 8, 512>);
+        case ck(RES_FAST, 2048, 4, 256): return go(k_res_fwdy_fast_2d<E, 2048, 4, 256>);
+        case ck(RES_FAST, 4096, 8, 1024): return go(k_res_fwdy_fast_2d<E, 4096, 8, 1024>);
+        case ck(RES_FAST, 4096, 4, 512): return go(k_res_fwdy_fast_2d<E, 4096, 4, 512>);
+        case ck(RES_FAST, 8192, 4, 1024): return go(k_res_fwdy_fast_2d<E, 8192, 4, 1024>);
+      } else switch (ck(k)) {
+        case ck(RES_FAST64, 4096, 4, 512): return go(k_res_fwdy_fast_2d<E, 4096, 4, 512, double>);
+        case ck(RES_FAST64, 2048, 4, 256): return go(k_res_fwdy_fast_2d<E, 2048, 4, 256, double>);
+        case ck(RES_FAST64, 2048, 4, 512): return go(k_res_fwdy_fast_2d<E, 2048, 4, 512, double>);
+      }
+      return no_kernel("res", k);
     });
   }
 
@@ -652,188 +630,120 @@ struct Impl : ImplBase {
   // p.nb blocks); p.xt_phase selects the sweeps (t-slab)
   int launch_precond(const KP<R>& p, int nblk = -1) {   // nblk: blocks [p.b0, p.b0 + nblk) (default: all)
     if (nblk < 0) nblk = p.nb - p.b0;
-    const dim3 g(nblk);
     ProfScope ps(this, "precond");
-    const bool one_row = p.T == 1 && !p.slab && p.xt_phase == 0 && pp.t1_xt;   // no t carries (k_precond_x_t1_2d)
-    if constexpr (sizeof(R) == 4) {
-      if (pp.fast_xt && !pp.half_real && one_row) {   // two workgroups per CU
-        const size_t lds = (size_t)((p.B / 2) * (p.nx + p.nx / 16) + twlds_size(p.nx)) * sizeof(C);
-        switch (p.nx) {
-          case 4096: return launch(k_precond_x_t1_2d<4096, 1, 512>, g, dim3(512), lds, p, twx);
-          case 2048: return launch(k_precond_x_t1_2d<2048, 2, 512>, g, dim3(512), lds, p, twx);
-          case 1024: return launch(k_precond_x_t1_2d<1024, 4, 512>, g, dim3(512), lds, p, twx);
-          case 512: return launch(k_precond_x_t1_2d<512, 8, 512>, g, dim3(512), lds, p, twx);
-          default: return fail(PDHG_ERR_UNSUPPORTED, "no one-row x kernel for nx=%d", p.nx);
-        }
-      }
-      if (pp.fast_xt) {
-        const size_t lds = pp.lds_fast_xt, ldsb = pp.lds_batch_xt;
-        if (pp.fast_xt_code == 5)   // static LDS (kernels_xt_dma.hpp, HR)
-          return launch(k_precond_xt_dma_2d<4096, true>, g, dim3(1024), 0, p, twx);
-        if (pp.fast_xt_code >= 3) switch (p.nx) {   // row-batched
-          case 4096:
-            if (pp.xt_dma)   // static LDS (kernels_xt_dma.hpp)
-              return launch(k_precond_xt_dma_2d<4096>, g, dim3(1024), 0, p, twx);
-            if (pp.xt_pair)   // RB = 2 rows, 512 threads: two workgroups per CU
-              return launch(k_precond_xt_batch_2d<4096, 1, 2, 0, 512>, g, dim3(512),
-                            (size_t)(2 * (4096 + 4096 / 16) + twlds_size(p.nx)) * sizeof(C), p, twx);
-            if (pp.xt_rpre == 2) return launch(k_precond_xt_batch_2d<4096, 1, 4, 2>, g, dim3(1024), ldsb, p, twx);
-            return launch(k_precond_xt_batch_2d<4096, 1>, g, dim3(1024), ldsb, p, twx);
-          case 2048: return launch(k_precond_xt_batch_2d<2048, 2>, g, dim3(1024), ldsb, p, twx);
-          case 1024: return launch(k_precond_xt_batch_2d<1024, 4>, g, dim3(1024), ldsb, p, twx);
-          case 512: return launch(k_precond_xt_batch_2d<512, 8>, g, dim3(1024), ldsb, p, twx);
-          default: return fail(PDHG_ERR_UNSUPPORTED, "no batched x kernel for nx=%d", p.nx);
-        }
-        if (pp.fast_xt_code == 2) switch (p.nx) {   // warp-specialised
-          case 8192: return launch(k_precond_xt_ws_2d<4096, 1, true>, g, dim3(512), lds, p, twx);
-          case 4096: return launch(k_precond_xt_ws_2d<4096, 1>, g, dim3(512), lds, p, twx);
-          case 2048: return launch(k_precond_xt_ws_2d<2048, 2>, g, dim3(512), lds, p, twx);
-          case 1024: return launch(k_precond_xt_ws_2d<1024, 4>, g, dim3(512), lds, p, twx);
-          case 512: return launch(k_precond_xt_ws_2d<512, 8>, g, dim3(512), lds, p, twx);
-          default: return fail(PDHG_ERR_UNSUPPORTED, "no fast x kernel for nx=%d", p.nx);
-        }
-        switch (p.nx) {   // single-role
-          case 4096: return launch(k_precond_xt_fast_2d<4096, 1, 512>, g, dim3(512), lds, p, twx);
-          case 2048: return launch(k_precond_xt_fast_2d<2048, 2, 512>, g, dim3(512), lds, p, twx);
-          case 1024: return launch(k_precond_xt_fast_2d<1024, 4, 512>, g, dim3(512), lds, p, twx);
-          case 512: return launch(k_precond_xt_fast_2d<512, 8, 512>, g, dim3(512), lds, p, twx);
-          default: return fail(PDHG_ERR_UNSUPPORTED, "no fast x kernel for nx=%d", p.nx);
-        }
-      }
-    } else {
-      // fp64 one-row window (the reference's marching default in its own precision): the carry-free x transform.
-      // Measured (C2 marching, nx = 2048, B = 2): the generic kernel took
-      // 156 us per launch, this one 28 us (67 MB read + 67 MB written: 4.8 TB/s)
-      if (pp.t1_xt64 && one_row) {
-        // G16 (nx = 2048 / 4096, t1_g16): only the first twiddled pass's 48 seeds in LDS, so 4 (nx = 2048, 256
-        // threads) or 2 (nx = 4096, 512 threads) workgroups fit a CU instead of 3 / 1
-        const bool g16 = pp.t1_g16;
-        const size_t lds = (size_t)((p.B / 2) * (p.nx + p.nx / 16) + (g16 ? 48 : twlds_size(p.nx))) * sizeof(C);
-        switch (p.nx) {
-          case 4096:
-            if (g16) return launch(k_precond_x_t1_2d<4096, 1, 512, double, true>, g, dim3(512), lds, p, twx);
-            return launch(k_precond_x_t1_2d<4096, 1, 512, double>, g, dim3(512), lds, p, twx);
-          case 2048:   // 512 threads: 28.06 vs 27.64 us (3 workgroups per CU by LDS)
-            if (g16) return launch(k_precond_x_t1_2d<2048, 1, 256, double, true>, g, dim3(256), lds, p, twx);
-            return launch(k_precond_x_t1_2d<2048, 1, 256, double>, g, dim3(256), lds, p, twx);
-          case 1024: return launch(k_precond_x_t1_2d<1024, 2, 512, double>, g, dim3(512), lds, p, twx);
-          case 512: return launch(k_precond_x_t1_2d<512, 4, 512, double>, g, dim3(512), lds, p, twx);
-          default: return fail(PDHG_ERR_UNSUPPORTED, "no fp64 one-row x kernel for nx=%d", p.nx);
-        }
-      }
-      if (pp.f64_xt) {
-        if (pp.half_real)   // nx = 8192: one real column per block + the split-twiddle tables
-          return launch(k_precond_xt_f64_2d<4096, 512, true>, g, dim3(512),
-                        (size_t)(Pad<4096>::LINE + TwLds<4096>::SIZE + 4096 + 128) * sizeof(C), p, twx);
-        if (p.nx == 1024)   // b' in registers, 4 items per thread
-          return launch(k_precond_xt_f64_2d<1024, 256, false, true>, g, dim3(256),
-                        (size_t)(Pad<1024>::LINE + TwLds<1024>::SIZE) * sizeof(C), p, twx);
-        if (p.nx == 512)
-          return launch(k_precond_xt_f64_2d<512, 128, false, true>, g, dim3(128),
-                        (size_t)(Pad<512>::LINE + TwLds<512>::SIZE) * sizeof(C), p, twx);
-        if (p.nx == 2048) {   // b' in registers (IT = 4 at 512 threads; PDHG_XT64_VAR: A/B of the shapes)
-          const size_t bpr = (size_t)(Pad<2048>::LINE + TwLds<2048>::SIZE) * sizeof(C);
-          switch (pp.xt64_var) {
-            case 1: return launch(k_precond_xt_f64_2d<2048, 256, false, false>, g, dim3(256), bpr + 2048 * sizeof(C), p, twx);
-            case 2: return launch(k_precond_xt_f64_2d<2048, 256, false, true>, g, dim3(256), bpr, p, twx);
-            case 3: return launch(k_precond_xt_f64_2d<2048, 1024, false, true>, g, dim3(1024), bpr, p, twx);
-            default: return launch(k_precond_xt_f64_2d<2048, 512, false, true>, g, dim3(512), bpr, p, twx);
-          }
-        }
-        if (pp.xt64_dma) {   // b' in registers, forward rows staged by LDS DMA: static LDS (kernels_xt_f64.hpp, DMA)
-          if (p.rspec) return launch(k_precond_xt_f64_2d<4096, 512, false, true, true, true>, g, dim3(512), 0, p, twx);
-          return launch(k_precond_xt_f64_2d<4096, 512, false, true, false, true>, g, dim3(512), 0, p, twx);
-        }
-        if (pp.xt64_bpr) {   // b' in registers alone (A/B: spills in the forward sweep)
-          const size_t ldsr = (size_t)(Pad<4096>::LINE + TwLds<4096>::SIZE) * sizeof(C);
-          if (p.rspec) return launch(k_precond_xt_f64_2d<4096, 512, false, true, true>, g, dim3(512), ldsr, p, twx);
-          return launch(k_precond_xt_f64_2d<4096, 512, false, true>, g, dim3(512), ldsr, p, twx);
-        }
-        const size_t lds = (size_t)(Pad<4096>::LINE + TwLds<4096>::SIZE + 4096) * sizeof(C);
-        if (p.rspec)   // task-order residual spectrum in (tc_spec; b' / x rows in `work` as always)
-          return launch(k_precond_xt_f64_2d<4096, 512, false, false, true>, g, dim3(512), lds, p, twx);
-        return launch(k_precond_xt_f64_2d<4096, 512>, g, dim3(512), lds, p, twx);
-      }
+    const KernelChoice& k = pp.xt_one_row.family ? pp.xt_one_row : pp.xt;   // a one-row window has no t carries
+    auto go = [&](auto kern) { return launch(kern, dim3(nblk), dim3(k.threads), k.lds, p, twx); };
+    if (k.family == XT_GENERIC)
+      return with_xt_fft([&](auto f) {
+        return launch(k_precond_xt_2d<R, decltype(f)>, dim3(nblk), dim3(k.threads), k.lds, p, f, twx);
+      });
+    if constexpr (sizeof(R) == 4) switch (ck(k)) {
+      case ck(XT1_F32, 4096, 1, 512): return go(k_precond_x_t1_2d<4096, 1, 512>);
+      case ck(XT1_F32, 2048, 2, 512): return go(k_precond_x_t1_2d<2048, 2, 512>);
+      case ck(XT1_F32, 1024, 4, 512): return go(k_precond_x_t1_2d<1024, 4, 512>);
+      case ck(XT1_F32, 512, 8, 512): return go(k_precond_x_t1_2d<512, 8, 512>);
+      case ck(XT_DMA_HR, 4096): return go(k_precond_xt_dma_2d<4096, true>);
+      case ck(XT_DMA, 4096): return go(k_precond_xt_dma_2d<4096>);
+      case ck(XT_BATCH, 4096, 1, 2, 0): return go(k_precond_xt_batch_2d<4096, 1, 2, 0, 512>);
+      case ck(XT_BATCH, 4096, 1, 4, 2): return go(k_precond_xt_batch_2d<4096, 1, 4, 2>);
+      case ck(XT_BATCH, 4096, 1, 4, 0): return go(k_precond_xt_batch_2d<4096, 1>);
+      case ck(XT_BATCH, 2048, 2, 4, 0): return go(k_precond_xt_batch_2d<2048, 2>);
+      case ck(XT_BATCH, 1024, 4, 4, 0): return go(k_precond_xt_batch_2d<1024, 4>);
+      case ck(XT_BATCH, 512, 8, 4, 0): return go(k_precond_xt_batch_2d<512, 8>);
+      case ck(XT_WS, 4096, 1, 1): return go(k_precond_xt_ws_2d<4096, 1, true>);
+      case ck(XT_WS, 4096, 1, 0): return go(k_precond_xt_ws_2d<4096, 1>);
+      case ck(XT_WS, 2048, 2, 0): return go(k_precond_xt_ws_2d<2048, 2>);
+      case ck(XT_WS, 1024, 4, 0): return go(k_precond_xt_ws_2d<1024, 4>);
+      case ck(XT_WS, 512, 8, 0): return go(k_precond_xt_ws_2d<512, 8>);
+      case ck(XT_FAST, 4096, 1, 512): return go(k_precond_xt_fast_2d<4096, 1, 512>);
+      case ck(XT_FAST, 2048, 2, 512): return go(k_precond_xt_fast_2d<2048, 2, 512>);
+      case ck(XT_FAST, 1024, 4, 512): return go(k_precond_xt_fast_2d<1024, 4, 512>);
+      case ck(XT_FAST, 512, 8, 512): return go(k_precond_xt_fast_2d<512, 8, 512>);
+    } else switch (ck(k)) {   // XT_F64's c: BPR 1 | TC 2 | DMA 4
+      case ck(XT1_F64_G16, 4096, 1, 512): return go(k_precond_x_t1_2d<4096, 1, 512, double, true>);
+      case ck(XT1_F64, 4096, 1, 512): return go(k_precond_x_t1_2d<4096, 1, 512, double>);
+      case ck(XT1_F64_G16, 2048, 1, 256): return go(k_precond_x_t1_2d<2048, 1, 256, double, true>);
+      case ck(XT1_F64, 2048, 1, 256): return go(k_precond_x_t1_2d<2048, 1, 256, double>);
+      case ck(XT1_F64, 1024, 2, 512): return go(k_precond_x_t1_2d<1024, 2, 512, double>);
+      case ck(XT1_F64, 512, 4, 512): return go(k_precond_x_t1_2d<512, 4, 512, double>);
+      case ck(XT_F64, 4096, 512, 1, 0): return go(k_precond_xt_f64_2d<4096, 512, true>);
+      case ck(XT_F64, 1024, 256, 0, 1): return go(k_precond_xt_f64_2d<1024, 256, false, true>);
+      case ck(XT_F64, 512, 128, 0, 1): return go(k_precond_xt_f64_2d<512, 128, false, true>);
+      case ck(XT_F64, 2048, 256, 0, 0): return go(k_precond_xt_f64_2d<2048, 256, false, false>);
+      case ck(XT_F64, 2048, 256, 0, 1): return go(k_precond_xt_f64_2d<2048, 256, false, true>);
+      case ck(XT_F64, 2048, 1024, 0, 1): return go(k_precond_xt_f64_2d<2048, 1024, false, true>);
+      case ck(XT_F64, 2048, 512, 0, 1): return go(k_precond_xt_f64_2d<2048, 512, false, true>);
+      case ck(XT_F64, 4096, 512, 0, 1 | 2 | 4): return go(k_precond_xt_f64_2d<4096, 512, false, true, true, true>);
+      case ck(XT_F64, 4096, 512, 0, 1 | 4): return go(k_precond_xt_f64_2d<4096, 512, false, true, false, true>);
+      case ck(XT_F64, 4096, 512, 0, 1 | 2): return go(k_precond_xt_f64_2d<4096, 512, false, true, true>);
+      case ck(XT_F64, 4096, 512, 0, 1): return go(k_precond_xt_f64_2d<4096, 512, false, true>);
+      case ck(XT_F64, 4096, 512, 0, 2): return go(k_precond_xt_f64_2d<4096, 512, false, false, true>);
+      case ck(XT_F64, 4096, 512, 0, 0): return go(k_precond_xt_f64_2d<4096, 512>);
     }
-    return with_xt_fft([&](auto f) {
-      return launch(k_precond_xt_2d<R, decltype(f)>, g, dim3(pp.NT2), pp.lds_xt, p, f, twx);
-    });
+    return no_kernel(pp.xt_one_row.family ? "xt_one_row" : "xt", k);
   }
 
   // ---------------- primal: update ----------------
   // inverse transforms + phi / phi_bar update of a 2-D window; returns its partial-row count through upd_rows
   int launch_update_2d(const KP<R>& p, int& upd_rows) {
     ProfScope ps(this, "update");
-    const dim3 gf(pp.g_fast_upd);
-    upd_rows = pp.g_fast_upd;
-    if constexpr (sizeof(R) == 8) {
-      if (pp.res64) {
-        if (pb.ny == 2048 && pp.upd_t1 > 0) {   // one-row windows: 256 threads, two workgroups per CU (G16 seeds)
-          const size_t lds = pp.lds_res64 + (size_t)48 * sizeof(C);
-          if (pp.upd_t1 == 2) return launch(k_invy_update_fast_2d<2048, 4, 256, 2, double, true>, gf, dim3(256), lds, p, twy);
-          return launch(k_invy_update_fast_2d<2048, 4, 256, 4, double, true>, gf, dim3(256), lds, p, twy);
-        }
-        if (pp.upd64_pair) {   // pairs of x-adjacent 4-row tasks (grid and partial rows: the pair count's)
-          auto go = [&](auto PFc) {
-            constexpr int PF_ = decltype(PFc)::value;
-            if (pb.ny == 4096) return launch(k_invy_update_pair_2d<4096, 512, PF_>, gf, dim3(512), pp.lds_upd64, p, twy);
-            return launch(k_invy_update_pair_2d<2048, 512, PF_>, gf, dim3(512), pp.lds_upd64, p, twy);
-          };
-          switch (pp.upd_pair_pf) {
-            case 2: return go(IC<2>{});
-            case 3: return go(IC<3>{});
-            default: return go(IC<4>{});
-          }
-        }
-        if (pb.ny == 4096) return launch(k_invy_update_fast_2d<4096, 4, 512, 4, double>, gf, dim3(512), pp.lds_upd64, p, twy);
-        return launch(k_invy_update_fast_2d<2048, 4, 512, 4, double>, gf, dim3(512), pp.lds_upd64, p, twy);
-      }
-      if (pp.upd8192)   // fp64 ny = 8192, half-real x blocks: 2-row tasks on one padded line
-        return launch(k_invy_update_fast_2d<8192, 2, 512, 2, double>, gf, dim3(512),
-                      (size_t)Pad<8192>::LINE * sizeof(C), p, twy);
-    }
-    if constexpr (kMixed) {   // the fp32 shapes with double phi rows; one prefetch depth (kMixedUpdPF) at 512 threads
-      if (pp.fast_rows)
-        return with_fast_rows([&](auto Nc, auto RWc, auto NTc) {
-          constexpr int N_ = decltype(Nc)::value, RW_ = decltype(RWc)::value, NT_ = decltype(NTc)::value;
-          if constexpr (NT_ == 1024 && RW_ == 8) {
-            if (pp.upd_threads == 512)
-              return launch(k_invy_update_fast_mixed_2d<N_, RW_, 512, kMixedUpdPF>, gf, dim3(512), pp.lds_fast_tw, p,
-                            twy, px);
-          }
-          return launch(k_invy_update_fast_mixed_2d<N_, RW_, NT_>, gf, dim3(NT_), pp.lds_fast_tw, p, twy, px);
-        });
+    const KernelChoice& k = pp.upd;
+    auto run = [&](auto kern, dim3 g, auto... fft) {   // the mixed kernels take the double phi pair (px) last
+      if constexpr (kMixed) return launch(kern, g, dim3(k.threads), k.lds, p, fft..., twy, px);
+      else return launch(kern, g, dim3(k.threads), k.lds, p, fft..., twy);
+    };
+    if (k.family == (kMixed ? UPD_GENERIC_MIXED : UPD_GENERIC)) {
       upd_rows = pp.gx4 * pp.g4;
       return with_line_fft(pp.ply, [&](auto f) {
         using F = decltype(f);
-        if (pp.nt_row <= 256)
-          return launch(k_invy_update_mixed_2d<F, 256>, dim3(pp.gx4), dim3(pp.nt_row), pp.lds_res, p, f, twy, px);
-        return launch(k_invy_update_mixed_2d<F, 1024>, dim3(pp.gx4), dim3(pp.nt_row), pp.lds_res, p, f, twy, px);
+        if constexpr (kMixed) {
+          if (k.b == 256) return run(k_invy_update_mixed_2d<F, 256>, dim3(pp.gx4), f);
+          return run(k_invy_update_mixed_2d<F, 1024>, dim3(pp.gx4), f);
+        } else {
+          if (k.b == 256) return run(k_invy_update_2d<R, F, 256>, dim3(pp.gx4), f);
+          return run(k_invy_update_2d<R, F, 1024>, dim3(pp.gx4), f);
+        }
       });
     }
-    if (pp.fast_rows)
-      return with_fast_rows([&](auto Nc, auto RWc, auto NTc) {
-        constexpr int N_ = decltype(Nc)::value, RW_ = decltype(RWc)::value, NT_ = decltype(NTc)::value;
-        if constexpr (sizeof(R) == 4) {
-          if constexpr (NT_ == 1024 && RW_ == 8) {
-            if (pp.upd_threads == 512) switch (pp.upd_pf) {
-              case 2: return launch(k_invy_update_fast_2d<N_, RW_, 512, 2>, gf, dim3(512), pp.lds_fast_tw, p, twy);
-              case 3: return launch(k_invy_update_fast_2d<N_, RW_, 512, 3>, gf, dim3(512), pp.lds_fast_tw, p, twy);
-              case 4: return launch(k_invy_update_fast_2d<N_, RW_, 512, 4>, gf, dim3(512), pp.lds_fast_tw, p, twy);
-              default: return launch(k_invy_update_fast_2d<N_, RW_, 512, 1>, gf, dim3(512), pp.lds_fast_tw, p, twy);
-            }
-          }
-          return launch(k_invy_update_fast_2d<N_, RW_, NT_>, gf, dim3(NT_), pp.lds_fast_tw, p, twy);
-        }
-        return (int)PDHG_OK;
-      });
-    upd_rows = pp.gx4 * pp.g4;
-    return with_line_fft(pp.ply, [&](auto f) {
-      using F = decltype(f);
-      if (pp.nt_row <= 256)
-        return launch(k_invy_update_2d<R, F, 256>, dim3(pp.gx4), dim3(pp.nt_row), pp.lds_res, p, f, twy);
-      return launch(k_invy_update_2d<R, F, 1024>, dim3(pp.gx4), dim3(pp.nt_row), pp.lds_res, p, f, twy);
-    });
+    upd_rows = pp.g_fast_upd;
+    auto go = [&](auto kern) { return run(kern, dim3(pp.g_fast_upd)); };
+    if constexpr (kMixed) switch (ck(k)) {   // the fp32 shapes with double phi rows; one PF (kMixedUpdPF) at 512 threads
+      case ck(UPD_FAST_MIXED, 256, 8, 64): return go(k_invy_update_fast_mixed_2d<256, 8, 64>);
+      case ck(UPD_FAST_MIXED, 512, 8, 128): return go(k_invy_update_fast_mixed_2d<512, 8, 128>);
+      case ck(UPD_FAST_MIXED, 1024, 8, 256): return go(k_invy_update_fast_mixed_2d<1024, 8, 256>);
+      case ck(UPD_FAST_MIXED, 2048, 8, 512): return go(k_invy_update_fast_mixed_2d<2048, 8, 512>);
+      case ck(UPD_FAST_MIXED, 2048, 4, 256): return go(k_invy_update_fast_mixed_2d<2048, 4, 256>);
+      case ck(UPD_FAST_MIXED, 4096, 8, 1024): return go(k_invy_update_fast_mixed_2d<4096, 8, 1024>);
+      case ck(UPD_FAST_MIXED, 4096, 8, 512, kMixedUpdPF): return go(k_invy_update_fast_mixed_2d<4096, 8, 512, kMixedUpdPF>);
+      case ck(UPD_FAST_MIXED, 4096, 4, 512): return go(k_invy_update_fast_mixed_2d<4096, 4, 512>);
+      case ck(UPD_FAST_MIXED, 8192, 4, 1024): return go(k_invy_update_fast_mixed_2d<8192, 4, 1024>);
+    } else if constexpr (sizeof(R) == 4) switch (ck(k)) {
+      case ck(UPD_FAST, 256, 8, 64): return go(k_invy_update_fast_2d<256, 8, 64>);
+      case ck(UPD_FAST, 512, 8, 128): return go(k_invy_update_fast_2d<512, 8, 128>);
+      case ck(UPD_FAST, 1024, 8, 256): return go(k_invy_update_fast_2d<1024, 8, 256>);
+      case ck(UPD_FAST, 2048, 8, 512): return go(k_invy_update_fast_2d<2048, 8, 512>);
+      case ck(UPD_FAST, 2048, 4, 256): return go(k_invy_update_fast_2d<2048, 4, 256>);
+      case ck(UPD_FAST, 4096, 8, 1024): return go(k_invy_update_fast_2d<4096, 8, 1024>);
+      case ck(UPD_FAST, 4096, 8, 512, 1): return go(k_invy_update_fast_2d<4096, 8, 512, 1>);
+      case ck(UPD_FAST, 4096, 8, 512, 2): return go(k_invy_update_fast_2d<4096, 8, 512, 2>);
+      case ck(UPD_FAST, 4096, 8, 512, 3): return go(k_invy_update_fast_2d<4096, 8, 512, 3>);
+      case ck(UPD_FAST, 4096, 8, 512, 4): return go(k_invy_update_fast_2d<4096, 8, 512, 4>);
+      case ck(UPD_FAST, 4096, 4, 512): return go(k_invy_update_fast_2d<4096, 4, 512>);
+      case ck(UPD_FAST, 8192, 4, 1024): return go(k_invy_update_fast_2d<8192, 4, 1024>);
+    } else switch (ck(k)) {
+      case ck(UPD_T1_G16, 2048, 4, 256, 2): return go(k_invy_update_fast_2d<2048, 4, 256, 2, double, true>);
+      case ck(UPD_T1_G16, 2048, 4, 256, 4): return go(k_invy_update_fast_2d<2048, 4, 256, 4, double, true>);
+      case ck(UPD_PAIR64, 4096, 0, 512, 2): return go(k_invy_update_pair_2d<4096, 512, 2>);
+      case ck(UPD_PAIR64, 4096, 0, 512, 3): return go(k_invy_update_pair_2d<4096, 512, 3>);
+      case ck(UPD_PAIR64, 4096, 0, 512, 4): return go(k_invy_update_pair_2d<4096, 512, 4>);
+      case ck(UPD_PAIR64, 2048, 0, 512, 2): return go(k_invy_update_pair_2d<2048, 512, 2>);
+      case ck(UPD_PAIR64, 2048, 0, 512, 3): return go(k_invy_update_pair_2d<2048, 512, 3>);
+      case ck(UPD_PAIR64, 2048, 0, 512, 4): return go(k_invy_update_pair_2d<2048, 512, 4>);
+      case ck(UPD_FAST64, 4096, 4, 512, 4): return go(k_invy_update_fast_2d<4096, 4, 512, 4, double>);
+      case ck(UPD_FAST64, 2048, 4, 512, 4): return go(k_invy_update_fast_2d<2048, 4, 512, 4, double>);
+      case ck(UPD_8192, 8192, 2, 512, 2): return go(k_invy_update_fast_2d<8192, 2, 512, 2, double>);
+    }
+    return no_kernel("upd", k);
   }
 
   // stages: 1 residual (+ forward y transform), 2 x transform + Thomas (sweeps per xt_phase: 0 both,
@@ -966,44 +876,43 @@ struct Impl : ImplBase {
   }
 
   // ---------------- dual ----------------
-  // fast dual over time rows [lo, hi); its partials start at block row zbase
+  // the row-per-thread / LDS-row dual over time rows [lo, hi); its partials start at block row zbase
   int launch_dual_fast(const KP<R>& p, int lo = 0, int hi = -1, int zbase = 0) {
     if (hi < 0) hi = pb.T;
     if (hi <= lo) return PDHG_OK;
     const dim3 g(pp.gxd, pp.gyd, (hi - lo + pp.jchunk_d - 1) / pp.jchunk_d);
+    // the sweep that also forms the next residual: in place, one time chunk, the whole window (a t-slab: its rows)
+    res_valid = pp.dual_fused.family && p.inplace && g.z == 1 && (slab || (lo == 0 && hi == pb.T));
+    const KernelChoice& k = res_valid ? pp.dual_fused : pp.dual;
     return with_egno<3>([&](auto eg) {
       constexpr int E = decltype(eg)::value;
-      auto sweep = [&](auto kern) { return launch(kern, g, dim3(pp.NTd), 0, p, pp.jchunk_d, lo, hi, zbase); };
-      if constexpr (kMixed) {   // row-per-thread only (plan_paths: dual_rx = 0, no fused residual)
-        if (pp.dual_rx || pp.fuse_res) return fail(PDHG_ERR_STATE, "mixed context planned an LDS-row dual");
-        res_valid = false;
-        if (pp.dual_one)
-          return launch(k_dual_fast_mixed_2d<E, 1>, g, dim3(pp.NTd), 0, p, pp.jchunk_d, lo, hi, zbase, px);
-        return launch(k_dual_fast_mixed_2d<E>, g, dim3(pp.NTd), 0, p, pp.jchunk_d, lo, hi, zbase, px);
+      auto go = [&](auto kern) {
+        if constexpr (kMixed) return launch(kern, g, dim3(k.threads), 0, p, pp.jchunk_d, lo, hi, zbase, px);
+        else return launch(kern, g, dim3(k.threads), 0, p, pp.jchunk_d, lo, hi, zbase);
+      };
+      if constexpr (kMixed) switch (ck(k)) {   // row-per-thread only (plan_paths: dual_rx = 0, no fused residual)
+        case ck(DUAL_ROW_MIXED, 0, 1): return go(k_dual_fast_mixed_2d<E, 1>);
+        case ck(DUAL_ROW_MIXED, 0, 0): return go(k_dual_fast_mixed_2d<E>);
+      } else if constexpr (sizeof(R) == 4) switch (ck(k)) {
+        case ck(DUAL_LDS_FR, 0, 8, 4):
+          if constexpr (E != 3) return go(k_dual_lds_2d<E, 8, true>);
+          break;
+        case ck(DUAL_LDS, 0, 4, 4): return go(k_dual_lds_2d<E, 4>);
+        case ck(DUAL_LDS, 0, 8, 4): return go(k_dual_lds_2d<E, 8>);
+        case ck(DUAL_LDS, 0, 16, 4): return go(k_dual_lds_2d<E, 16>);
+        case ck(DUAL_ROW, 0, 1): return go(k_dual_fast_2d<E, float, 1>);
+        case ck(DUAL_ROW, 0, 0): return go(k_dual_fast_2d<E>);
+      } else switch (ck(k)) {
+        case ck(DUAL_LDS_FR, 0, 8, 2):
+          if constexpr (E != 3) return go(k_dual_lds_2d<E, 8, true, double, 2>);
+          break;
+        case ck(DUAL_LDS, 0, 8, 2): return go(k_dual_lds_2d<E, 8, false, double, 2>);
+        case ck(DUAL_LDS, 0, 8, 4): return go(k_dual_lds_2d<E, 8, false, double>);
+        case ck(DUAL_ROW, 0, 2): return go(k_dual_fast_2d<E, double, 2>);
+        case ck(DUAL_ROW, 0, 1): return go(k_dual_fast_2d<E, double, 1>);
+        case ck(DUAL_ROW, 0, 0): return go(k_dual_fast_2d<E, double>);
       }
-      if constexpr (E != 3) {
-        if (pp.fuse_res && p.inplace && g.z == 1 && (slab || (lo == 0 && hi == pb.T))) {
-          int rc;
-          if constexpr (sizeof(R) == 4) rc = sweep(k_dual_lds_2d<E, 8, true>);
-          else rc = sweep(k_dual_lds_2d<E, 8, true, double, 2>);
-          res_valid = true;
-          return rc;
-        }
-      }
-      res_valid = false;
-      if constexpr (sizeof(R) == 4) {
-        switch (pp.dual_rx) {
-          case 4: return sweep(k_dual_lds_2d<E, 4>);
-          case 8: return sweep(k_dual_lds_2d<E, 8>);
-          case 16: return sweep(k_dual_lds_2d<E, 16>);
-          default: return pp.dual_one ? sweep(k_dual_fast_2d<E, float, 1>) : sweep(k_dual_fast_2d<E>);
-        }
-      } else {
-        if (pp.dual_rx == 8)
-          return pp.dual_ypl == 2 ? sweep(k_dual_lds_2d<E, 8, false, double, 2>) : sweep(k_dual_lds_2d<E, 8, false, double>);
-        if (pp.dual_one == 2) return sweep(k_dual_fast_2d<E, double, 2>);
-        return pp.dual_one ? sweep(k_dual_fast_2d<E, double, 1>) : sweep(k_dual_fast_2d<E, double>);
-      }
+      return no_kernel(res_valid ? "dual_fused" : "dual", k);
     });
   }
 
@@ -1042,7 +951,7 @@ struct Impl : ImplBase {
     ProfScope ps(this, "dual");
     const dim3 g(pp.gx5, pp.g5);
     nrows = pp.gx5 * pp.g5;
-    if (pb.ndim == 2 && pp.fast_dual) {
+    if (pb.ndim == 2 && pp.dual.family != (kMixed ? DUAL_POINT_MIXED : DUAL_POINT)) {
       nrows = pp.gxd * pp.gyd * pp.gzd;
       return launch_dual_fast(p);
     }

@@ -1,6 +1,7 @@
 // Which kernels a context runs and with what geometry: decided once, at context creation, by plan_paths() -- a pure
 // function of the problem, the precision, the decomposition and the Tuning (no device, no environment).  The
-// launchers (ctx_impl.hpp) read the PathPlan and re-test nothing; pdhg_path_info / pdhg_plan_info answer from it.
+// launchers (ctx_impl.hpp) switch on the plan's KernelChoice per stage and re-test nothing; pdhg_path_info /
+// pdhg_plan_info answer from the same choices.
 // The decisions are ordered: a later one reads the earlier ones' values (marked "reads" below).
 #pragma once
 
@@ -50,7 +51,33 @@ struct Decomp {
   bool mixed = false;   // precision 12: S = 4 with phi and phi_bar in double (single 2-D contexts)
 };
 
+// The kernel one 2-D stage launches: its family (the stage's enum below; 0: the stage has no such kernel), the
+// family's template integers (0 where unused), the block size and the dynamic LDS bytes as launched (0: static / none)
+struct KernelChoice {
+  int family = 0;
+  int n = 0, a = 0, b = 0, c = 0;
+  int threads = 0;
+  size_t lds = 0;
+};
+// The family codes are the values of the "<stage>_kernel" keys (include/pdhg.h); n, a, b, c
+// are the template integers the launcher's case names, in the kernel's own order where the family has one.
+// x transform.  fp32: XT_FAST <n, NL, NT>, XT_WS <n, NL, HR>, XT_BATCH <n, NL, RB, RPRE> (RB = 2: 512 threads), XT_DMA
+// and XT_DMA_HR (nx = 8192) <4096>; fp64 XT_F64 <n, NT, HR, flags>: BPR 1 | TC 2 | DMA 4; XT_GENERIC: the runtime-radix
+// kernel (with_xt_fft).  One-row windows: XT1_* <n, NL, NT> of k_precond_x_t1_2d (fp32, fp64, fp64 with G16)
+enum XtKernel { XT_NONE, XT_FAST, XT_WS, XT_BATCH, XT_DMA, XT_DMA_HR, XT_F64, XT_GENERIC, XT1_F32, XT1_F64, XT1_F64_G16 };
+// residual <n, RW, NT>: fp32 / fp64 fast rows, unfused and fused; RES_GENERIC b: the kernel's thread bound (256 / 1024)
+enum ResKernel { RES_NONE, RES_GENERIC, RES_FAST, RES_FAST64, RES_FUSED, RES_FUSED64 };
+// update <n, RW, NT, PF> (PF 0: the kernel's default): fp32 and mixed fast rows, the fp64 4-row kernel, its one-row
+// G16 form, the 8-row task pairs <n, -, NT, PF>, the 2-row tasks at ny = 8192; UPD_GENERIC*: b as RES_GENERIC
+enum UpdKernel { UPD_NONE, UPD_GENERIC, UPD_GENERIC_MIXED, UPD_FAST, UPD_FAST_MIXED, UPD_FAST64, UPD_T1_G16,
+                 UPD_PAIR64, UPD_8192 };
+// dual sweep: per point, row per thread (a: ONE), x rows through LDS (a: RX, b: YPL), ... forming the residual too
+enum DualKernel { DUAL_NONE, DUAL_POINT, DUAL_POINT_MIXED, DUAL_ROW, DUAL_ROW_MIXED, DUAL_LDS, DUAL_LDS_FR };
+
 struct PathPlan {
+  // what each 2-D stage launches (set at the end of the decision it belongs to; the launchers switch on these).
+  // xt_one_row: T = 1 single or x-slab contexts; res_fused / dual_fused: while the fused residual is valid / formed
+  KernelChoice xt, xt_one_row, res, res_fused, upd, dual, dual_fused;
   FFTPlan plx{}, ply{};   // x (global length) and y line transforms
   int na = 0, n_dead = 0;
   bool mixed = false;     // fp32 state and kernels, phi / phi_bar double (the mixed update and dual kernels)
@@ -64,24 +91,17 @@ struct PathPlan {
   int gx1 = 0, gx4 = 0, g4 = 1, gx5 = 0, g5 = 1, g_outer = 1;
   int head_xrun = 4;              // x rows per workgroup of the head form's chunk passes
   int nt_row = 256;               // threads of the generic 2-D row kernels (k_res_fwdy_2d, k_invy_update_2d)
-  int rows_var = 0;               // row-kernel shape variant (with_fast_rows)
-  int res64_nt = 512;             // fp64 fused residual threads at ny = 4096
-  int half_nt = 3;                // ny = 4096 row kernels with 512 threads (bit 0 residual, bit 1 update)
-  int upd_pf = 4;                 // update kernel (512 threads): old-phi row pairs in flight (1..4)
   int NTd = 256, gxd = 0, gyd = 0, gzd = 0, jchunk_d = 1;
   int gz_1d = 1, jchunk_1d = 1;   // 1-D fused residual (k_dual_1d_fr): time chunks of the dual sweep
   int nt1d = 256;                 // 1-D residual / update block size (1024 on the global-scratch path)
   int RWf = 8, NTf = 1024, g_fast_upd = 1;   // fast row kernels: rows per workgroup, threads, update grid
   size_t partial_rows = 0;
-  // LDS bytes
-  size_t lds_res = 0, lds_xt = 0, lds_batch_xt = 0, lds_fast_xt = 0, lds_fast = 0, lds_fast_tw = 0, lds_res64 = 0,
-         lds_upd64 = 0;
+  size_t lds_res = 0;             // LDS bytes of the generic row kernels and the 1-D line kernels
   // dual
   bool fast_dual = false;         // row-per-thread / LDS-row time-marching dual instead of the per-point kernel
   int dual_rx = 0;                // > 0: k_dual_lds_2d with dual_rx x rows per workgroup (x neighbours through LDS)
   int dual_ypl = 4;               // y per lane of k_dual_lds_2d (fp64: 4 or 2)
   int dual_order = 0;             // workgroup -> tile order of k_dual_lds_2d (dual_order.hpp: 0 x-fastest, XB > 0 band)
-  int dual_one = 0;               // as launched: k_dual_fast_2d<.., ONE> on one-row workgroups (0: marching form)
   bool dual_multi = false;        // rho_alp_iters > 1: the dual loop in chunks of sub-iterations
   bool dual_head = false;         // ... below 2^25 points: sub-iteration 0 alone, the rest in chunks
   bool k1_outer = true;           // one-sub-iteration loops skip the outer-sum pass
@@ -96,25 +116,10 @@ struct PathPlan {
   bool res64 = false;             // fp64 residual and update through the fast row kernels (4-row groups)
   bool ip_rows = false;           // fp64 ny = 8192: generic row kernels on one padded in-place line (FFTIp)
   bool upd8192 = false;           // fp64 ny = 8192, half-real x: update through the fast row kernel on 2-row tasks
-  bool upd64_pair = false;        // fp64 ny = 2048 / 4096: update on 8-row task pairs (k_invy_update_pair_2d)
-  int upd_pair_pf = 4;            // ... its old-phi row pairs in flight (2..4)
   bool tc_spec = false;           // fp64 C3: residual spectrum in task order (KP::rspec)
   bool to_c4 = false;             // C4 (half-real x blocks): fused residual in task order + transpose
-  int res_threads = 0, upd_threads = 0;   // as launched: fast row kernels' threads after half_nt (0: not the fast rows)
-  int res64_nt2048 = 512;         // fp64 unfused residual's threads at ny = 2048
-  int upd_t1 = 0;                 // fp64 ny = 2048 update on one-row windows: 256 threads + G16 seeds (2: PF 2, 1: PF 4)
   // x transform
-  bool t1_xt = true;              // T = 1 windows: carry-free x transform (k_precond_x_t1_2d)
-  bool fast_xt = false;           // fp32 power-of-two nx: the fast x kernels ...
-  int fast_xt_code = 0;           // ... as launched: 1 single-role, 2 warp-specialised, 3 batched, 4 DMA, 5 DMA half-real
-  bool xt_dma = false, xt_pair = false;   // the batched kernel's nx = 4096 forms
-  int xt_rpre = 0;
-  bool t1_xt64 = false;           // fp64 T = 1 windows: k_precond_x_t1_2d<..., double>
-  bool t1_g16 = false;            // as launched: ... with the later passes' twiddle seeds from global memory
   bool f64_xt = false;            // fp64: in-place line + register carries (k_precond_xt_f64_2d)
-  int xt64_var = 0;               // nx = 2048 shape of it (threads, b' in registers or LDS)
-  bool xt64_bpr = false;          // nx = 4096 form of it with b' / x in registers (8 items per thread)
-  bool xt64_dma = false;          // ... and the forward sweep's rows staged by LDS DMA (needs xt64_bpr's 64 KiB)
   // 1-D
   bool glb_line = false;          // line FFTs over global scratch (nx beyond LDS)
   bool fourstep = false;          // nx = 65536: four-step DHT
@@ -186,26 +191,23 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     // (reads B, half_real, f64_small)
     pl.f64_xt = S == 8 && pb.bc_x == 0 &&
                 (((nxg == 4096 || nxg == 2048) && B == 2) || (nxg == 8192 && pl.half_real) || f64_small) && xt64_on;
-    pl.xt64_var = tn.xt64_var;
     // nx = 4096 column pairs on single contexts (t-slab phases, x-slabs and the half-real blocks keep the LDS b'
     // line): b' / x in registers, and in the 64 KiB that frees the forward rows staged by LDS DMA, the first
     // radix-16 pass out of place (PDHG_XT64_DMA; PDHG_XT64_BPR=1 with PDHG_XT64_DMA=0: the register form alone,
     // A/B -- the DMA form cannot run without it, its staging line is the LDS b' line's space)
     // (reads f64_xt, half_real, B)
-    {
-      const bool ok = pl.f64_xt && nxg == 4096 && B == 2 && !pl.half_real && !slab && !xslab;
-      const bool dma = ok && tn.xt64_dma.value_or(1) != 0;
-      pl.xt64_bpr = ok && tn.xt64_bpr.value_or(dma ? 1 : 0) != 0;
-      pl.xt64_dma = dma && pl.xt64_bpr;
-    }
+    const bool bpr_ok = pl.f64_xt && nxg == 4096 && B == 2 && !pl.half_real && !slab && !xslab;
+    const bool dma_ok = bpr_ok && tn.xt64_dma.value_or(1) != 0;
+    const bool xt64_bpr = bpr_ok && tn.xt64_bpr.value_or(dma_ok ? 1 : 0) != 0;
+    const bool xt64_dma = dma_ok && xt64_bpr;
     // fp64 one-row windows at a power-of-two nx: the carry-free transform needs only the padded lines
-    pl.t1_xt64 = S == 8 && T == 1 && pb.bc_x == 0 && !pl.half_real && !slab && pl.plx.pow2 &&
-                 nxg >= 512 && nxg <= 4096 && nxg * (B / 2) == (nxg == 4096 ? 4096 : 2048);
+    const bool t1_xt64 = S == 8 && T == 1 && pb.bc_x == 0 && !pl.half_real && !slab && pl.plx.pow2 &&
+                         nxg >= 512 && nxg <= 4096 && nxg * (B / 2) == (nxg == 4096 ? 4096 : 2048);
     // fp64 unfused residual's threads at ny = 2048: 256 on one-row windows (two 4-wave workgroups per CU, 225 VGPRs;
     // C2's T = 1 residual 54 -> 47 us), 512 otherwise (C2's T = 100 unfused residual 4.66 vs 4.94 ms at 256)
-    pl.res64_nt2048 = tn.res64_nt2048.value_or(T == 1 ? 256 : 512);
+    const int res64_nt2048 = tn.res64_nt2048.value_or(T == 1 ? 256 : 512);
     // steady marching iteration 0.2196 (512 threads) / 0.2150 (PF 4) / 0.2131 ms (PF 2)
-    pl.upd_t1 = T == 1 ? tn.upd_t1.value_or(2) : 0;
+    const int upd_t1 = T == 1 ? tn.upd_t1.value_or(2) : 0;
     if (!pl.half_real && !pl.f64_xt && (size_t)nxg * B > cap)
       return fail(PDHG_ERR_UNSUPPORTED, "nx=%d too large for the x-transform slab (max %zu in this precision)", nxg,
                   cap / 2);
@@ -214,7 +216,6 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     pl.nb = (ny + B - 1) / B;
     pl.lds_res = 2 * (size_t)ny * csz;
     const int nmodes = nxg * B;
-    pl.lds_xt = (size_t)5 * nmodes * S;
     // fp64 ny = 8192 (C4's y extent in the reference's precision): the generic row kernels transform the row pair
     // in place in one padded line (FFTIp, 136 KiB) instead of a Stockham ping-pong of two (256 KiB)
     pl.ip_rows = S == 8 && ny == 8192 && pl.lds_res > kLdsBytes && !xslab;
@@ -233,7 +234,6 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     pl.gx4 = (int)std::min<long long>((long long)pl.gx1, 4096);
     pl.gx5 = (ny + 255) / 256;
     pl.g5 = std::max(1, std::min(T * nx, 8192 / std::max(1, pl.gx5)));
-    pl.t1_xt = tn.t1_xt;
     pl.k1_outer = tn.k1_outer;
     pl.fold_fin = tn.fold_fin;
     // short windows (the reference's T = 1 marching default): few time rows per workgroup leave little to
@@ -243,35 +243,74 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     // fused residual beats the fused 8-row sweep (200 VGPRs, 2 waves/SIMD) at T = 1 (0.31 vs 0.41 ms),
     // ties at T = 4 and loses from T = 8 on.
     const bool short_win = T < tn.short_t_xt, short_dual = T < tn.short_t_dual;
-    bool ws_xt = false, batch_xt = false, xt_dma_hr = false;
+    const int NL = B / 2;
+    const size_t pad4k = 4096 + 4096 / 16;   // a padded line of 4096 complex
+    // the generic runtime-radix kernel unless a fast form below applies: FFT ping-pong + Thomas carries
+    pl.xt = {XT_GENERIC, 0, 0, 0, 0, pl.NT2, (size_t)5 * nmodes * S};
+    bool fast_xt = false;   // fp32 power-of-two nx: the fast x kernels
     if (pl.half_real && S == 4) {
-      pl.fast_xt = true;
-      ws_xt = true;
-      // the LDS-DMA staged x transform on half-real blocks (k_precond_xt_dma_2d<4096, true>) for windows of >= 4
-      // rows: c4w50 x transform 28.4 ms with the warp-specialised kernel (round 4, 1.9 TB/s)
-      xt_dma_hr = tn.xt_dma_hr ? *tn.xt_dma_hr != 0 : T >= 4;
-      pl.lds_fast_xt = (size_t)(2 * (4096 + 4096 / 16) + 816 + 4096) * csz;   // + split twiddles
-    } else if (S == 4 && pl.plx.pow2 && nxg * (B / 2) == 4096 && nxg >= 512 && pb.bc_x == 0) {
-      pl.fast_xt = true;
+      fast_xt = true;
+      // the LDS-DMA staged x transform on half-real blocks (k_precond_xt_dma_2d<4096, true>, static LDS) for windows
+      // of >= 4 rows: c4w50 x transform 28.4 ms with the warp-specialised kernel (round 4, 1.9 TB/s)
+      if (tn.xt_dma_hr ? *tn.xt_dma_hr != 0 : T >= 4) pl.xt = {XT_DMA_HR, 4096, 0, 0, 0, 1024, 0};
+      else pl.xt = {XT_WS, 4096, 1, 1, 0, 512, (2 * pad4k + 816 + 4096) * csz};   // + split twiddles
+    } else if (S == 4 && pl.plx.pow2 && nxg * NL == 4096 && nxg >= 512 && pb.bc_x == 0) {
+      fast_xt = true;
       // the other widths spill registers in the warp-specialised form
-      ws_xt = tn.xt_ws ? *tn.xt_ws != 0 : (nxg == 4096) && !short_win;
+      const bool ws_xt = tn.xt_ws ? *tn.xt_ws != 0 : (nxg == 4096) && !short_win;
       // row-batched x transform (k_precond_xt_batch_2d): 4 rows per transform, 1024 threads.  Measured at C3
       // (nx = 4096, T = 200): 16.2 -> 14.5 ms against the warp-specialised kernel; at C2 (nx = 2048,
       // T = 100) 2.07 -> 1.82 ms against the single-role one.  nx = 1024 / 512 spill in it: not selected.
-      batch_xt = tn.xt_batch ? *tn.xt_batch != 0 : (nxg == 4096 || nxg == 2048) && T >= 4;
-      pl.xt_rpre = tn.xt_rpre;
-      pl.xt_pair = tn.xt_pair;
-      // LDS-DMA staged rows (k_precond_xt_dma_2d) at nx = 4096: C3 14.24 -> 13.52 ms
-      pl.xt_dma = nxg == 4096 && tn.xt_dma.value_or(1) != 0;
-      pl.lds_batch_xt = (size_t)(4 * (4096 + 4096 / 16) + twlds_size(nxg)) * csz;
-      // padded FFT buffer + theta, E, b' (float2 per item) + twiddle seeds (TwLds<nx>)
-      pl.lds_fast_xt = ws_xt ? (size_t)(2 * (4096 + 4096 / 16) + 816) * csz
-                             : (size_t)(4096 + 4096 / 16 + 3 * 4096 + 816) * csz;
+      const bool batch_xt = tn.xt_batch ? *tn.xt_batch != 0 : (nxg == 4096 || nxg == 2048) && T >= 4;
+      const size_t tw = twlds_size(nxg);
+      if (batch_xt && nxg == 4096 && tn.xt_dma.value_or(1) != 0)
+        // LDS-DMA staged rows (k_precond_xt_dma_2d, static LDS) at nx = 4096: C3 14.24 -> 13.52 ms
+        pl.xt = {XT_DMA, 4096, 0, 0, 0, 1024, 0};
+      else if (batch_xt && nxg == 4096 && tn.xt_pair)   // RB = 2 rows, 512 threads: two workgroups per CU
+        pl.xt = {XT_BATCH, 4096, 1, 2, 0, 512, (2 * pad4k + tw) * csz};
+      else if (batch_xt)
+        pl.xt = {XT_BATCH, nxg, NL, 4, (nxg == 4096 && tn.xt_rpre == 2) ? 2 : 0, 1024, (4 * pad4k + tw) * csz};
+      else if (ws_xt)
+        pl.xt = {XT_WS, nxg, NL, 0, 0, 512, (2 * pad4k + 816) * csz};
+      else   // padded FFT buffer + theta, E, b' (float2 per item) + twiddle seeds (TwLds<nx>)
+        pl.xt = {XT_FAST, nxg, NL, 512, 0, 512, (pad4k + 3 * 4096 + 816) * csz};
     }
-    // (an x-slab reports its local row count here, as pdhg_path_info always has)
-    pl.fast_xt_code = !pl.fast_xt ? 0 : (pl.half_real && xt_dma_hr) ? 5
-                      : (batch_xt && !pl.half_real) ? ((pl.xt_dma && pb.nx == 4096) ? 4 : 3) : ws_xt ? 2 : 1;
-    pl.t1_g16 = pl.t1_xt64 && pl.t1_xt && tn.t1_g16 && (nxg == 2048 || nxg == 4096);
+    // fp64: the forms of k_precond_xt_f64_2d (reads f64_xt, half_real, xt64_bpr, xt64_dma; tc_spec sets TC below)
+    if (pl.f64_xt) {
+      const size_t tw4k = TwLds<4096>::SIZE;
+      if (pl.half_real)   // nx = 8192: one real column per block + the split-twiddle tables
+        pl.xt = {XT_F64, 4096, 512, 1, 0, 512, (Pad<4096>::LINE + tw4k + 4096 + 128) * csz};
+      else if (nxg == 1024)   // b' in registers, 4 items per thread
+        pl.xt = {XT_F64, 1024, 256, 0, 1, 256, (size_t)(Pad<1024>::LINE + TwLds<1024>::SIZE) * csz};
+      else if (nxg == 512)
+        pl.xt = {XT_F64, 512, 128, 0, 1, 128, (size_t)(Pad<512>::LINE + TwLds<512>::SIZE) * csz};
+      else if (nxg == 2048) {   // b' in registers (IT = 4 at 512 threads; PDHG_XT64_VAR: A/B of the shapes)
+        const size_t bpr = (size_t)(Pad<2048>::LINE + TwLds<2048>::SIZE) * csz;
+        const int v = tn.xt64_var;   // 1: 256 threads with b' in LDS, 2: 256, 3: 1024
+        const int nt = (v == 1 || v == 2) ? 256 : v == 3 ? 1024 : 512;
+        pl.xt = {XT_F64, 2048, nt, 0, v == 1 ? 0 : 1, nt, v == 1 ? bpr + 2048 * csz : bpr};
+      } else if (xt64_dma)   // b' in registers, forward rows staged by LDS DMA: static LDS (kernels_xt_f64.hpp, DMA)
+        pl.xt = {XT_F64, 4096, 512, 0, 1 | 4, 512, 0};
+      else if (xt64_bpr)   // b' in registers alone (A/B: spills in the forward sweep)
+        pl.xt = {XT_F64, 4096, 512, 0, 1, 512, (Pad<4096>::LINE + tw4k) * csz};
+      else
+        pl.xt = {XT_F64, 4096, 512, 0, 0, 512, (Pad<4096>::LINE + tw4k + 4096) * csz};
+    }
+    // one-row windows (T = 1 single and x-slab contexts; a t-slab runs its phases): the carry-free x transform
+    // k_precond_x_t1_2d on the padded lines + twiddle seeds, two workgroups per CU.  fp64 (the reference's marching
+    // default in its own precision; C2 marching, nx = 2048, B = 2: the generic kernel took 156 us per launch, this one
+    // 28 us, 67 MB read + 67 MB written: 4.8 TB/s), G16 at nx = 2048 / 4096: only the first twiddled pass's 48 seeds
+    // in LDS, so 4 (nx = 2048, 256 threads; 512: 28.06 vs 27.64 us) or 2 (nx = 4096) workgroups fit a CU, not 3 / 1
+    // (reads fast_xt, half_real, t1_xt64)
+    if (T == 1 && !slab && tn.t1_xt) {
+      const size_t lines = (size_t)NL * (nxg + nxg / 16);
+      const bool g16 = tn.t1_g16 && (nxg == 2048 || nxg == 4096);
+      if (S == 4 && fast_xt && !pl.half_real)
+        pl.xt_one_row = {XT1_F32, nxg, NL, 512, 0, 512, (lines + twlds_size(nxg)) * csz};
+      else if (t1_xt64)
+        pl.xt_one_row = {g16 ? XT1_F64_G16 : XT1_F64, nxg, NL, nxg == 2048 ? 256 : 512, 0, nxg == 2048 ? 256 : 512,
+                         (lines + (g16 ? 48 : twlds_size(nxg))) * csz};
+    }
     // fp64: the row-per-thread time-marching dual (k_dual_fast_2d<EGNO, double>) instead of the generic
     // per-point kernel, which re-reads every phi_bar neighbour (fp64 C3: 248 GB fetched for 161 GB of reads).
     // Measured at fp64 C3 (same box, profiles/r04_ab_dual64_*.json): 52.7 vs 59.3 ms per dual, 6.61 vs 6.44
@@ -301,15 +340,17 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
       pl.jchunk_d = (T + nJ0 - 1) / nJ0;
       pl.gzd = (T + pl.jchunk_d - 1) / pl.jchunk_d;
     }
-    pl.dual_one = (pl.fast_dual && !pl.dual_rx && pl.jchunk_d == 1) ? dual_one : 0;
-    pl.rows_var = tn.rows_var;
-    pl.half_nt = tn.half_nt;
-    pl.res64_nt = tn.res64_nt;
-    pl.upd_pf = tn.upd_pf;
+    // k_dual_fast_2d<.., ONE> on one-row workgroups (0: the marching form; fp64 2: 4 waves per SIMD)
+    dual_one = (pl.fast_dual && !pl.dual_rx && pl.jchunk_d == 1) ? (dual_one == 2 && S == 8 && !dc.mixed ? 2 : dual_one != 0)
+                                                                 : 0;
+    // generic row kernels (the line FFT policy: with_line_fft), replaced below where the fast rows apply
+    pl.res = {RES_GENERIC, 0, 0, pl.nt_row <= 256 ? 256 : 1024, 0, pl.nt_row, pl.lds_res};
+    pl.upd = {dc.mixed ? UPD_GENERIC_MIXED : UPD_GENERIC, 0, 0, pl.nt_row <= 256 ? 256 : 1024, 0, pl.nt_row, pl.lds_res};
+    size_t lds_fast_tw = 0;   // fp32 fast rows: the lines + the persistent kernels' twiddle seeds
     if (S == 4 && pl.ply.pow2 && ny >= 256 && ny <= 8192) {
       pl.RWf = (ny == 8192) ? 4 : 8;
       pl.NTf = std::min(1024, ny / 4);
-      if (pl.rows_var == 1 && (ny == 4096 || ny == 2048)) {   // 4 rows / block, 2 blocks per CU
+      if (tn.rows_var == 1 && (ny == 4096 || ny == 2048)) {   // 4 rows / block, 2 blocks per CU
         pl.RWf = 4;
         pl.NTf = ny / 8;
       }
@@ -321,22 +362,33 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
           const int v = *tn.tile_j;
           if (v >= 1 && (v == 1 || (nx / pl.RWf) % 4 == 0)) pl.tile_j = v;
         }
-        pl.lds_fast = (size_t)(pl.RWf / 2) * (ny + ny / 16) * csz;
+        const size_t lds_fast = (size_t)(pl.RWf / 2) * (ny + ny / 16) * csz;
         // + the twiddle-seed table of the persistent kernels (fused residual, update; ny <= 4096)
-        pl.lds_fast_tw = pl.lds_fast + (ny <= 4096 ? (size_t)twlds_size(ny) * csz : 0);
+        lds_fast_tw = lds_fast + (ny <= 4096 ? (size_t)twlds_size(ny) * csz : 0);
         pl.g_fast_upd = std::min((nx / pl.RWf) * T, 2048);
+        pl.res = {RES_FAST, ny, pl.RWf, pl.NTf, 0, pl.NTf, lds_fast};
+        // ny = 4096 8-row update with 512 threads (PDHG_HALF_NT bit 1) and PF old-phi row pairs in flight (1..4;
+        // mixed: kMixedUpdPF)
+        const bool half = pl.NTf == 1024 && pl.RWf == 8 && (tn.half_nt & 2);
+        const int pf = dc.mixed ? kMixedUpdPF : (tn.upd_pf >= 2 && tn.upd_pf <= 4) ? tn.upd_pf : 1;
+        const int nt = half ? 512 : pl.NTf;
+        pl.upd = {dc.mixed ? UPD_FAST_MIXED : UPD_FAST, ny, pl.RWf, nt, half ? pf : 0, nt, lds_fast_tw};
       }
     }
     // fp64 residual: the fast row kernel on 4-row groups (2 complex lines of 4096 doubles = 136 KiB of LDS),
     // rows read once per group over the sliding 3-row window, instead of the generic row-pair kernel's
     // per-point neighbour re-reads (fp64 C3: 204 GB moved against 80.5 GB algorithmic)
+    size_t lds_upd64 = 0;
     if (S == 8 && pl.ply.pow2 && (ny == 2048 || ny == 4096) && nx % 4 == 0) {
       pl.res64 = tn.res64.value_or(1) != 0;
       if (pl.res64) {
         pl.tile_j = ((nx / 4) % 4 == 0) ? 8 : 1;
-        pl.lds_res64 = (size_t)2 * (ny + ny / 16) * csz;
+        // 1024 threads cap the fp64 rows at 128 VGPRs (spills): 512, or res64_nt2048 at ny = 2048
+        const size_t lds_res64 = (size_t)2 * (ny + ny / 16) * csz;
+        const int nt = ny == 2048 && res64_nt2048 == 256 ? 256 : 512;
+        pl.res = {RES_FAST64, ny, 4, nt, 0, nt, lds_res64};
         // the update through the fast row kernel too: + the twiddle-seed table (152 KiB at ny = 4096)
-        pl.lds_upd64 = pl.lds_res64 + (size_t)twlds_size(ny) * csz;
+        lds_upd64 = lds_res64 + (size_t)twlds_size(ny) * csz;
         pl.g_fast_upd = std::min((nx / 4) * T, 2048);
         // the update on pairs of x-adjacent 4-row tasks (k_invy_update_pair_2d: whole 128-B spectrum lines, the second
         // task's half held in registers across the first; bitwise the 4-row kernel's phi' / phi_bar): single contexts
@@ -347,13 +399,20 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
         // (a loss), so by default windows of >= 100 rows only; PDHG_UPD_PAIR=1 any window, =0 the 4-row kernel
         // (reads B, upd_t1)
         const bool pair_ok = !slab && !xslab && (nx / 4) % 2 == 0 && T >= 1 && B >= 2 && B <= 16 && ny % B == 0 &&
-                             !(ny == 2048 && pl.upd_t1 > 0);
-        pl.upd64_pair = pair_ok && (tn.upd_pair ? *tn.upd_pair != 0 : T >= 100);
-        pl.upd_pair_pf = tn.upd_pair_pf;
-        if (pl.upd64_pair) pl.g_fast_upd = std::min((nx / 8) * T, 2048);
+                             !(ny == 2048 && upd_t1 > 0);
+        const bool upd64_pair = pair_ok && (tn.upd_pair ? *tn.upd_pair != 0 : T >= 100);
+        if (upd64_pair) pl.g_fast_upd = std::min((nx / 8) * T, 2048);   // the pair count's grid and partial rows
         if (tn.upd_grid) pl.g_fast_upd = std::min(pl.g_fast_upd, *tn.upd_grid);
+        if (ny == 2048 && upd_t1 > 0)   // one-row windows: 256 threads, two workgroups per CU (G16 seeds); PF 2 / 4
+          pl.upd = {UPD_T1_G16, 2048, 4, 256, upd_t1 == 2 ? 2 : 4, 256, lds_res64 + 48 * csz};
+        else if (upd64_pair)   // its old-phi row pairs in flight (2..4)
+          pl.upd = {UPD_PAIR64, ny, 0, 512, tn.upd_pair_pf, 512, lds_upd64};
+        else
+          pl.upd = {UPD_FAST64, ny, 4, 512, 4, 512, lds_upd64};
       }
     }
+    if (pl.upd8192)   // (its decision is above, with ip_rows) 2-row tasks on one padded line
+      pl.upd = {UPD_8192, 8192, 2, 512, 2, 512, (size_t)Pad<8192>::LINE * csz};
     // fp64 C3 shape: the residual spectrum handed to the x transform in task order (p.rspec; one contiguous run per
     // 4-row task instead of 64-B chunks of the blocked layout), the x kernel's forward sweep reading it
     // Interleaved A/B (round 5): C3's T = 200 118.8 -> 118.3 ms; its 25-row slab share (8 GPUs) 16.05 -> 16.35 ms
@@ -361,8 +420,9 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     // (never on one-row windows: the T = 1 x kernel reads the blocked work buffer)
     // (reads res64, f64_xt, half_real, B, t1_xt64)
     const bool tc_ok = S == 8 && pl.res64 && ny == 4096 && pl.f64_xt && !pl.half_real && nxg == 4096 && B == 2 &&
-                       !xslab && T > 1 && !pl.t1_xt64;
+                       !xslab && T > 1 && !t1_xt64;
     pl.tc_spec = tc_ok && (tn.tc_spec ? *tn.tc_spec != 0 : T >= 100);
+    if (pl.tc_spec) pl.xt.c |= 2;   // the nx = 4096 forms of k_precond_xt_f64_2d with the task-order input (TC)
     // fused residual: fp32 fast kernels with 8-row tiles on both sides, rho_alp_iters = 1 (in place),
     // periodic bc, egno 1/2, single context; each dual workgroup must march the whole window (the
     // residual row j needs rho'_{j+1}), so only grids with enough (x, y) tiles to fill the chip
@@ -388,8 +448,20 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
         }
         pl.jchunk_d = T;
         pl.gzd = 1;
+        // the residual kernel that completes the rows the sweep formed: fp32 the fast rows' shape (ny = 4096 / 8192
+        // with 512 threads per PDHG_HALF_NT bit 0); fp64 4-row tasks (ny = 4096: PDHG_RES64_NT=1024, A/B: 16 waves per
+        // CU, GPT = 1), at ny = 8192 quarter-tile tasks on one padded line of 8192 complex doubles
+        const int nt = S == 4 ? ((pl.NTf == 1024 && (tn.half_nt & 1)) ? 512 : pl.NTf) : ny == 4096 ? tn.res64_nt : 512;
+        if (S == 4) pl.res_fused = {RES_FUSED, ny, pl.RWf, nt, 0, nt, lds_fast_tw};
+        else if (ny == 8192) pl.res_fused = {RES_FUSED64, 8192, 2, nt, 0, nt, (size_t)Pad<8192>::LINE * csz};
+        else pl.res_fused = {RES_FUSED64, ny, 4, nt, 0, nt, lds_upd64};
+        pl.dual_fused = {DUAL_LDS_FR, 0, 8, pl.dual_ypl, 0, pl.NTd, 0};
       }
     }
+    // the sweep without the fused residual (reads fast_dual, dual_rx, dual_one and dual_ypl after the overwrite)
+    if (!pl.fast_dual) pl.dual = {dc.mixed ? DUAL_POINT_MIXED : DUAL_POINT, 0, 0, 0, 0, 256, 0};
+    else if (pl.dual_rx) pl.dual = {DUAL_LDS, 0, pl.dual_rx, pl.dual_ypl, 0, pl.NTd, 0};
+    else pl.dual = {dc.mixed ? DUAL_ROW_MIXED : DUAL_ROW, 0, dual_one, 0, 0, pl.NTd, 0};
     // workgroup -> tile order of k_dual_lds_2d (PDHG_DUAL_ORDER; dual_order.hpp): the band order (XB = 1, each XCD's
     // workgroups across whole grid rows) for the fused sweep on the 2048^2 and 4096^2 grids, where every freshly
     // created context ran the dual below the x-fastest order's median (interleaved A/B, 4 contexts each,
@@ -406,11 +478,6 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
     pl.to_c4 = pl.fuse_res && pl.half_real && B == 1 && ny == 8192 && !xslab &&
                (S == 8 ? pl.ip_rows : (pl.fast_rows && pl.RWf == 4)) && (nx % (S == 8 ? 64 : 128)) == 0 &&
                tn.c4_to.value_or(1) != 0;
-    // threads of the fast row kernels as launched (ny = 4096: 512 instead of 1024 per half_nt); reads fuse_res
-    if (pl.fast_rows) {
-      pl.res_threads = (pl.NTf == 1024 && (pl.half_nt & 1) && pl.fuse_res) ? 512 : pl.NTf;
-      pl.upd_threads = (pl.NTf == 1024 && pl.RWf == 8 && (pl.half_nt & 2)) ? 512 : pl.NTf;
-    }
   } else {
     pl.lds_res = 2 * (size_t)nx * csz;
     pl.gx1 = (T + 1) / 2;
@@ -488,8 +555,20 @@ inline int plan_paths(const pdhg_problem& pb, int S, const Decomp& dc, const Tun
   return PDHG_OK;
 }
 
-// the creation-time keys of pdhg_path_info / pdhg_plan_info (S = sizeof(real), ny / nx: the context's own)
+// the creation-time keys of pdhg_path_info / pdhg_plan_info (S = sizeof(real), pb: the context's own problem).  What
+// runs is read off the stage's KernelChoice; "<stage>_kernel" is its family code, "<stage>_shape" its threads
 inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const std::string& k, int* value) {
+  const KernelChoice *stage[] = {&pl.xt, &pl.xt_one_row, &pl.res, &pl.res_fused, &pl.upd, &pl.dual, &pl.dual_fused};
+  const char* stage_name[] = {"xt", "xt_one_row", "res", "res_fused", "upd", "dual", "dual_fused"};
+  for (int i = 0; i < 7; ++i) {
+    if (k == std::string(stage_name[i]) + "_kernel") return *value = stage[i]->family, true;
+    if (k == std::string(stage_name[i]) + "_shape") return *value = stage[i]->threads, true;
+    const int shape[] = {stage[i]->n, stage[i]->a, stage[i]->b, stage[i]->c};   // "<stage>_n" / "_a" / "_b" / "_c"
+    for (int j = 0; j < 4; ++j)
+      if (k == std::string(stage_name[i]) + "_" + "nabc"[j]) return *value = shape[j], true;
+  }
+  const bool lds_dual = pl.dual.family == DUAL_LDS, xt64_4k = pl.xt.family == XT_F64 && pl.xt.n == 4096 && !pl.xt.b;
+  const bool fast_upd = pl.upd.family == UPD_FAST || pl.upd.family == UPD_FAST_MIXED;
   if (k == "fused_residual") *value = pl.fuse_res ? 1 : 0;
   else if (k == "mixed") *value = pl.mixed ? 1 : 0;   // precision 12; the other keys: the fp32 kernels chosen
   else if (k == "fast_rows") *value = pl.fast_rows ? 1 : 0;
@@ -498,33 +577,39 @@ inline bool plan_key(const PathPlan& pl, const pdhg_problem& pb, int S, const st
   else if (k == "dual_head") *value = pl.dual_head ? 1 : 0;     // ... sub-iteration 0 alone, then the chunks
   else if (k == "spec") *value = pl.spec_ok ? 1 : 0;   // iterate(): speculative one-sub-iteration schedule allowed
   else if (k == "dual64") *value = (S == 8 && pl.fast_dual) ? 1 : 0;
-  else if (k == "fast_dual") *value = pl.fast_dual ? pl.dual_rx : -1;
-  else if (k == "dual_ypl") *value = pl.fast_dual && pl.dual_rx ? pl.dual_ypl : 0;
-  else if (k == "res64_nt") *value = pl.res64 ? (pb.ny == 2048 ? pl.res64_nt2048 : 512) : 0;
-  else if (k == "upd_t1") *value = (pl.res64 && pb.ny == 2048) ? pl.upd_t1 : 0;
-  else if (k == "t1_g16") *value = (pl.t1_g16 && (pb.nx == 2048 || pb.nx == 4096)) ? 1 : 0;
-  else if (k == "dual_one") *value = pl.dual_one ? 1 : 0;
-  else if (k == "fast_xt") *value = pl.fast_xt_code;
+  else if (k == "fast_dual") *value = lds_dual ? pl.dual.a : pl.dual.family >= DUAL_ROW ? 0 : -1;
+  else if (k == "dual_ypl") *value = lds_dual ? pl.dual.b : 0;
+  // fp64 4-row residual threads: the fused kernel's where PDHG_RES64_NT=1024 applies, else the unfused kernel's
+  else if (k == "res64_nt")
+    *value = pl.res.family != RES_FAST64 ? 0 : pl.res_fused.threads == 1024 ? 1024 : pl.res.threads;
+  else if (k == "upd_t1") *value = pl.upd.family == UPD_T1_G16 ? (pl.upd.c == 2 ? 2 : 1) : 0;
+  // (an x-slab context answers "t1_g16" and "fast_xt" 4 for its local row count, as it always has)
+  else if (k == "t1_g16") *value = (pl.xt_one_row.family == XT1_F64_G16 && pb.nx == pl.xt_one_row.n) ? 1 : 0;
+  else if (k == "dual_one") *value = (pl.dual.family == DUAL_ROW || pl.dual.family == DUAL_ROW_MIXED) && pl.dual.a;
+  else if (k == "fast_xt")   // the window kernel's fp32 fast family (XT_FAST .. XT_DMA_HR are the key's codes 1 .. 5)
+    *value = pl.xt.family > XT_DMA_HR ? 0 : (pl.xt.family == XT_DMA && pb.nx != 4096) ? (int)XT_BATCH : pl.xt.family;
   else if (k == "half_real") *value = pl.half_real ? 1 : 0;
   else if (k == "fourstep") *value = pl.fourstep ? 1 : 0;
   else if (k == "glb_line") *value = pl.glb_line ? 1 : 0;
   else if (k == "ip_rows") *value = pl.ip_rows ? 1 : 0;   // fp64 ny = 8192 row pairs in one padded line
-  else if (k == "upd8192") *value = pl.upd8192 ? 1 : 0;   // fp64 ny = 8192: 2-row fast update
-  else if (k == "upd64_pair") *value = pl.upd64_pair ? 1 : 0;   // fp64 ny = 2048 / 4096: update on 8-row task pairs
+  else if (k == "upd8192") *value = pl.upd.family == UPD_8192;   // fp64 ny = 8192: 2-row fast update
+  else if (k == "upd64_pair") *value = pl.upd.family == UPD_PAIR64;   // fp64 ny = 2048 / 4096: update on 8-row task pairs
   else if (k == "upd_grid") *value = pl.g_fast_upd;   // workgroups of the fast update kernels
   else if (k == "tc_spec") *value = pl.tc_spec ? 1 : 0;   // fp64 C3: task-order residual spectrum
   else if (k == "to_c4") *value = pl.to_c4 ? 1 : 0;       // C4: task-order residual spectrum + transpose
   else if (k == "thomas_chunk") *value = pl.thomas_chunk ? 1 : 0;
   else if (k == "fs_wide") *value = (pl.fourstep && pl.fs_wide && !pl.fs16) ? 1 : 0;
   else if (k == "fs16") *value = pl.fs16 ? 1 : 0;
-  else if (k == "rows_rw") *value = pl.fast_rows ? pl.RWf : 0;   // rows per fast row-kernel workgroup
+  else if (k == "rows_rw") *value = pl.res.family == RES_FAST ? pl.res.a : 0;   // rows per fast row-kernel workgroup
   else if (k == "row_threads") *value = pl.nt_row;
-  else if (k == "res_threads") *value = pl.res_threads;
-  else if (k == "upd_threads") *value = pl.upd_threads;
-  else if (k == "f64_xt") *value = pl.f64_xt ? 1 : 0;   // fp64 nx = 4096 x transform (kernels_xt_f64.hpp)
-  else if (k == "xt64_dma") *value = pl.xt64_dma ? 1 : 0;   // ... nx = 4096: forward rows by LDS DMA, b' in registers
-  else if (k == "xt64_bpr") *value = pl.xt64_bpr ? 1 : 0;   // ... nx = 4096: b' / x in registers
-  else if (k == "t1_xt64") *value = (pl.t1_xt64 && pl.t1_xt) ? 1 : 0;   // fp64 T = 1: carry-free x transform
+  // fp32 fast rows as launched: the fused residual's threads where it runs, else the unfused kernel's
+  else if (k == "res_threads")
+    *value = pl.res.family != RES_FAST ? 0 : pl.res_fused.family ? pl.res_fused.threads : pl.res.threads;
+  else if (k == "upd_threads") *value = fast_upd ? pl.upd.threads : 0;
+  else if (k == "f64_xt") *value = pl.f64_xt ? 1 : 0;   // fp64 nx = 512 .. 8192 x transform (kernels_xt_f64.hpp)
+  else if (k == "xt64_dma") *value = xt64_4k && (pl.xt.c & 4);   // ... nx = 4096: forward rows by LDS DMA, b' in registers
+  else if (k == "xt64_bpr") *value = xt64_4k && (pl.xt.c & 1);        // ... nx = 4096: b' / x in registers
+  else if (k == "t1_xt64") *value = pl.xt_one_row.family == XT1_F64 || pl.xt_one_row.family == XT1_F64_G16;   // fp64 T = 1: carry-free x transform
   else if (k == "report_tile") *value = pl.report_tile ? 1 : 0;         // pdhg_report_state: the tile kernel
   else if (k == "report_wgs") *value = pl.report_tile ? pl.report_wgs : 0;   // ... its workgroup target
   else return false;

@@ -149,6 +149,17 @@ int validate_problem(const pdhg_problem& p) {
   return PDHG_OK;
 }
 
+// a single context of one Impl type in its box (kept there on failure too: the box's destructor frees it)
+template <typename I>
+int make_impl(CtxBox& box, const pdhg_problem& p, int device) {
+  auto im = std::make_unique<I>();
+  im->pb = p;
+  im->device = device;
+  const int rc = im->setup();
+  box.impl = std::move(im);
+  return rc;
+}
+
 }  // namespace
 
 extern "C" {
@@ -180,25 +191,9 @@ int pdhg_create(const pdhg_problem* prob, int device, pdhg_ctx** out) {
   if (device < 0 || device >= ndev) return fail(PDHG_ERR_ARG, "device %d out of range (%d devices)", device, ndev);
   auto box = std::make_unique<CtxBox>();
   box->precision = p.precision;
-  if (p.precision == 8) {
-    auto im = std::make_unique<Impl<double>>();
-    im->pb = p;
-    im->device = device;
-    rc = im->setup();
-    box->impl = std::move(im);
-  } else if (p.precision == kMixedPrecision) {
-    auto im = std::make_unique<Impl<float, double>>();
-    im->pb = p;
-    im->device = device;
-    rc = im->setup();
-    box->impl = std::move(im);
-  } else {
-    auto im = std::make_unique<Impl<float>>();
-    im->pb = p;
-    im->device = device;
-    rc = im->setup();
-    box->impl = std::move(im);
-  }
+  if (p.precision == 8) rc = make_impl<Impl<double>>(*box, p, device);
+  else if (p.precision == kMixedPrecision) rc = make_impl<Impl<float, double>>(*box, p, device);
+  else rc = make_impl<Impl<float>>(*box, p, device);
   if (rc) return rc;
   *out = reinterpret_cast<pdhg_ctx*>(box.release());
   return PDHG_OK;

@@ -214,6 +214,15 @@ ONE_STEP = {
     "dma_fr_4096x256": (2, 4096, 256, 8, {"PDHG_XT_BATCH": "1", "PDHG_XT_DMA": "1", "PDHG_FUSE_RES": "1"},
                         {"fast_xt": 4, "fused_residual": 1}),
     "dma_4096_T7": (1, 4096, 256, 7, {"PDHG_XT_BATCH": "1", "PDHG_XT_DMA": "1"}, {"fast_xt": 4}),   # odd T
+    # the fp32 row kernels' A/B shapes at the smallest grid that selects them (16 x rows: two 8-row groups)
+    "rows_rw4_ny2048": (2, 16, 2048, 3, {"PDHG_ROWS_VAR": "1"}, {"rows_rw": 4, "upd_threads": 256}),
+    "rows_rw4_ny4096": (2, 16, 4096, 3, {"PDHG_ROWS_VAR": "1"}, {"rows_rw": 4, "upd_threads": 512}),
+    "upd_pf1_ny4096": (2, 16, 4096, 3, {"PDHG_UPD_PF": "1"}, {"rows_rw": 8, "upd_threads": 512, "upd_c": 1}),
+    "upd_pf2_ny4096": (2, 16, 4096, 3, {"PDHG_UPD_PF": "2"}, {"rows_rw": 8, "upd_threads": 512, "upd_c": 2}),
+    "upd_pf3_ny4096": (2, 16, 4096, 3, {"PDHG_UPD_PF": "3"}, {"rows_rw": 8, "upd_threads": 512, "upd_c": 3}),
+    "upd_nt1024_ny4096": (2, 16, 4096, 3, {"PDHG_HALF_NT": "1"}, {"rows_rw": 8, "upd_threads": 1024, "upd_c": 0}),
+    "res_fr_nt1024_ny8192": (2, 16, 8192, 3, {"PDHG_FUSE_RES": "1", "PDHG_HALF_NT": "2"},
+                             {"fused_residual": 1, "res_threads": 1024, "res_fused_kernel": 4, "res_fused_shape": 1024}),
 }
 
 
@@ -376,8 +385,12 @@ FP64_CASES = {
     # default at C3's size, forced on the fixture's smaller grid
     "c3_rows_ny4096+fr": {"res64": 1, "dual64": 1, "fused_residual": 1, "dual_ypl": 2},
     "c2_rows_ny2048+fr": {"res64": 1, "dual64": 1, "fused_residual": 1, "dual_ypl": 2},
+    # ... its ny = 4096 form with 1024 threads (k_res_fwdy_fused_2d<.., 4096, 4, 1024, double>, PDHG_RES64_NT=1024)
+    "c3_rows_ny4096+nt1024": {"res64": 1, "fused_residual": 1, "res_fused_kernel": 5, "res_fused_shape": 1024,
+                              "res64_nt": 1024},
 }
 FP64_ENV = {"fr": {"PDHG_FUSE_RES": "1", "PDHG_SHORT_T": "0"}, "generic": {"PDHG_XT64": "0"},
+           "nt1024": {"PDHG_FUSE_RES": "1", "PDHG_SHORT_T": "0", "PDHG_RES64_NT": "1024"},
            "v1": {"PDHG_XT64_VAR": "1"}, "v2": {"PDHG_XT64_VAR": "2"}, "v3": {"PDHG_XT64_VAR": "3"}}
 FP64_BAR = 1e-9
 

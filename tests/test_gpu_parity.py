@@ -720,3 +720,22 @@ def test_fused_1d_residual(native, monkeypatch, parity_log, prec, egno, T, epsl)
         b["alp"] = 2e-3  # oracle itself: 9.4e-4 from the float64 one): rounding-level changes
     parity_log("test_fused_1d_residual", "e{}_65536_T{}_eps{}@{}".format(egno, T, epsl, prec), m, b)
     assert all(m[k] <= b[k] for k in m), (m, b)
+
+
+@pytest.mark.parametrize("prec,ny,T", [("fp32", 256, 3), ("fp64", 2048, 1), ("mixed", 4096, 3)],
+                         ids=["fp32_16x256_T3", "fp64_16x2048_T1", "mixed_16x4096_T3"])
+def test_kernel_choice_keys_match_the_plan(native, prec, ny, T):
+    """A context answers the "<stage>_kernel" / "<stage>_shape" keys (what its launchers switch on) as pdhg_plan_info
+    does for the same problem and environment without a device."""
+    import ctypes
+    P = make_problem(1, 2, 16, ny, T, 0.0)
+    ctx = device_ctx(P, prec)
+    try:
+        for stage in ("xt", "xt_one_row", "res", "res_fused", "upd", "dual", "dual_fused"):
+            for key in (stage + "_kernel", stage + "_shape"):
+                v = ctypes.c_int(-1)
+                native.check(native.load().pdhg_plan_info(ctypes.byref(ctx._prob), key.encode(), ctypes.byref(v)))
+                assert ctx.path_info(key) == v.value, (key, ctx.path_info(key), v.value)
+        assert ctx.path_info("res_kernel") == {"fp32": 2, "fp64": 3, "mixed": 2}[prec]
+    finally:
+        ctx.close()

@@ -78,13 +78,23 @@ KERNELS = {
     "fast1_512": _k("fp32", 2, 512, 32, T_MULTI, (2, 13), [(_B0, {"fast_xt": 1})]),
     "fast1_1024": _k("fp32", 1, 1024, 32, T_MULTI, (3, 6), [(_B0, {"fast_xt": 1})]),
     "fast1_2048": _k("fp32", 2, 2048, 32, T_MULTI, (2, 13), [(_B0, {"fast_xt": 1})]),
+    "fast1_4096": _k("fp32", 2, 4096, 32, T_MULTI, (3,), [(_B0, {"fast_xt": 1, "xt_n": 4096})]),
     # ---- fp32 warp-specialised k_precond_xt_ws_2d (fast_xt = 2); PDHG_SHORT_T_XT=0 selects it below T = 16
+    **{"ws_{}".format(n): _k("fp32", 2, n, 32, T_MULTI, (3,), [({"PDHG_XT_BATCH": "0", "PDHG_XT_WS": "1"},
+                                                                         {"fast_xt": 2, "xt_kernel": 2, "xt_n": n})])
+       for n in (512, 1024, 2048)},   # the narrower widths, selectable with PDHG_XT_WS=1 only
     "ws_4096": _k("fp32", 2, 4096, 32, T_MULTI, (3, 13),
                   [({"PDHG_XT_BATCH": "0", "PDHG_SHORT_T_XT": "0"}, {"fast_xt": 2, "half_real": 0})]),
     "ws_hr_8192": _k("fp32", 2, 8192, 32, T_ALL, (1, 6), [({"PDHG_XT_DMA_HR": "0"}, {"fast_xt": 2, "half_real": 1})]),
     # ---- fp32 row-batched k_precond_xt_batch_2d (fast_xt = 3)
     "batch_2048": _k("fp32", 2, 2048, 32, T_BATCH, (5, 6), [({}, {"fast_xt": 3})]),
     "batch_4096": _k("fp32", 1, 4096, 32, T_BATCH, (4, 7), [({"PDHG_XT_DMA": "0"}, {"fast_xt": 3})]),
+    **{"batch_{}".format(n): _k("fp32", 2, n, 32, T_BATCH, (5,), [({"PDHG_XT_BATCH": "1"}, {"fast_xt": 3, "xt_n": n})])
+       for n in (512, 1024)},   # selectable with PDHG_XT_BATCH=1 only
+    "batch_4096_pair": _k("fp32", 2, 4096, 32, T_BATCH, (5,), [({"PDHG_XT_DMA": "0", "PDHG_XT_PAIR": "1"},
+                                                                   {"fast_xt": 3, "xt_b": 2, "xt_shape": 512})]),
+    "batch_4096_rpre2": _k("fp32", 2, 4096, 32, T_BATCH, (5,), [({"PDHG_XT_DMA": "0", "PDHG_XT_RPRE": "2"},
+                                                                    {"fast_xt": 3, "xt_b": 4, "xt_c": 2})]),
     # ---- fp32 LDS-DMA k_precond_xt_dma_2d (fast_xt = 4; half-real 5)
     "dma_4096": _k("fp32", 2, 4096, 32, T_BATCH, T_BATCH, [({}, {"fast_xt": 4, "half_real": 0})], bench=True),
     "dma_hr_8192": _k("fp32", 2, 8192, 32, T_BATCH, (5, 13), [({}, {"fast_xt": 5, "half_real": 1})]),

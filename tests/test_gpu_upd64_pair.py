@@ -33,7 +33,7 @@ PAIRED = [(8, 4096, 1, None, True), (16, 4096, 3, None, False), (40, 4096, 2, No
 IDS = ["{}x{}_T{}{}".format(c[0], c[1], c[2], "_grid{}".format(c[3]) if c[3] else "") for c in PAIRED]
 
 
-def _run(P, monkeypatch, flag, want_pair, grid=None):
+def _run(P, monkeypatch, flag, want_pair, grid=None, pf=4):
     """phi' and phi_bar after one update_primal from the seeded state, then the stop statistics of the first iteration
     from it and phi, phi_bar and the statistics after the third, with PDHG_UPD_PAIR = flag."""
     monkeypatch.setenv("PDHG_UPD_PAIR", flag)
@@ -41,6 +41,9 @@ def _run(P, monkeypatch, flag, want_pair, grid=None):
     try:
         got = {k: ctx.path_info(k) for k in ("res64", "upd64_pair")}
         assert got == {"res64": 1, "upd64_pair": want_pair}, (flag, got)
+        if want_pair:   # k_invy_update_pair_2d<ny, 512, PF>
+            got = {k: ctx.path_info(k) for k in ("upd_kernel", "upd_n", "upd_c")}
+            assert got == {"upd_kernel": 7, "upd_n": P["ny"], "upd_c": pf}, got
         if grid is not None:
             assert ctx.path_info("upd_grid") == grid
         ctx.set_stop_rules(converge=False, nan=False)
@@ -91,6 +94,20 @@ def test_pair_form_bitwise(native, monkeypatch, parity_log, case):
         assert m["rel_" + k] <= bound, (k, m, bound)
     if oracle:
         assert m["phi_vs_oracle"] <= 1e-9, m
+
+
+@pytest.mark.parametrize("ny", [2048, 4096])
+@pytest.mark.parametrize("pf", [2, 3])
+def test_pair_prefetch_depths_bitwise(native, monkeypatch, ny, pf):
+    """PDHG_UPD_PAIR_PF = 2 / 3 (old-phi row pairs in flight; the default is 4): the depth changes when rows are loaded,
+    not what is computed, so phi' and phi_bar are the 4-row kernel's bit for bit, as in test_pair_form_bitwise."""
+    monkeypatch.setenv("PDHG_UPD_PAIR_PF", str(pf))
+    P = make_problem(EGNO, 2, 16, ny, 3, EPSL, seeded=True)
+    new = _run(P, monkeypatch, "1", 1, pf=pf)
+    old = _run(P, monkeypatch, "0", 0)
+    for k in ("phi1", "phi_bar1", "phi3", "phi_bar3"):
+        assert np.all(np.isfinite(new[k])) and float(np.max(np.abs(new[k]))) > 0.0, k
+        assert np.array_equal(new[k], old[k]), k
 
 
 def test_odd_task_count_keeps_the_four_row_kernel(native, monkeypatch, parity_log):

@@ -68,6 +68,34 @@ def test_fp64_task_order_spectrum(native, monkeypatch, parity_log, fuse):
     assert all(m[k] <= 1e-13 for k in m if k != "bitwise"), m
 
 
+@pytest.mark.parametrize("form,env,xt_c", [("lds", {"PDHG_XT64_DMA": "0"}, 0), ("bpr", {"PDHG_XT64_DMA": "0", "PDHG_XT64_BPR": "1"}, 1)])
+def test_fp64_task_order_spectrum_x_forms(native, monkeypatch, parity_log, form, env, xt_c):
+    """The task-order input (TC) on the two nx = 4096 forms of the x kernel without the LDS-DMA staging -- b' in LDS and
+    b' in registers -- against the blocked layout on the same form, as test_fp64_task_order_spectrum does for the
+    default form and at its bound; a 3-row window, 3 iterations.  "xt_c" is BPR 1 | TC 2 | DMA 4."""
+    for k, v in dict(env, PDHG_FUSE_RES="1", PDHG_SHORT_T="0").items():
+        monkeypatch.setenv(k, v)
+    P = make_problem(2, 2, 4096, 4096, 3, 0.0, seeded=True)
+    out = {}
+    for flag in ("1", "0"):
+        monkeypatch.setenv("PDHG_TC_SPEC", flag)
+        ctx = device_ctx(P, "fp64")
+        try:
+            got = {k: ctx.path_info(k) for k in ("xt_kernel", "xt_n", "xt_c", "tc_spec", "fused_residual")}
+            assert got == {"xt_kernel": 6, "xt_n": 4096, "xt_c": xt_c | (2 if flag == "1" else 0), "tc_spec": int(flag),
+                           "fused_residual": 1}, got
+            ctx.set_state(P["phi"], P["rho"], P["alp"])
+            st = ctx.iterate(3, TAU, SIGMA, -1.0, 1)
+            out[flag] = (ctx.get_state(), st)
+        finally:
+            ctx.close()
+    (s1, st1), (s0, st0) = out["1"], out["0"]
+    m = {"phi": rel(s1[0], s0[0]), "rho": rel(s1[1], s0[1]), "alp": max(rel(a, b) for a, b in zip(s1[2], s0[2])),
+         "err1": abs(st1["err1"] - st0["err1"]) / st0["err1"]}
+    parity_log("test_fp64_task_order_spectrum_x_forms", "c3_4096x4096_T3_" + form, m, {k: 1e-13 for k in m})
+    assert all(v <= 1e-13 for v in m.values()), m
+
+
 def test_fp64_task_order_spectrum_primal_twice(native, monkeypatch, parity_log):
     """Drop-in pairing the loop never makes: two update_primal calls in a row after a fused dual sweep.  With the
     task-order spectrum stored over the R plane (tc_spec + fused residual) the first primal consumes R, so the

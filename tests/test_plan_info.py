@@ -20,7 +20,8 @@ ENV_USED = ("PDHG_FUSE_RES", "PDHG_XT_BATCH", "PDHG_XT_DMA", "PDHG_XT_DMA_HR", "
             "PDHG_HALF_NT", "PDHG_FS16", "PDHG_FS_WIDE", "PDHG_THOMAS_CHUNK", "PDHG_XT64", "PDHG_XT64_VAR", "PDHG_RES64",
             "PDHG_DUAL64", "PDHG_RES64_NT2048", "PDHG_UPD_T1", "PDHG_TC_SPEC", "PDHG_UPD8192", "PDHG_C4_TO",
             "PDHG_T1_XT", "PDHG_T1_G16", "PDHG_FOURSTEP", "PDHG_FUSE_RES1D", "PDHG_SPEC", "PDHG_DUAL_ONE",
-            "PDHG_DUAL_HEAD", "PDHG_K1_OUTER", "PDHG_DUAL_MULTI", "PDHG_FOLD_FIN", "PDHG_ROWS_VAR")
+            "PDHG_DUAL_HEAD", "PDHG_K1_OUTER", "PDHG_DUAL_MULTI", "PDHG_FOLD_FIN", "PDHG_ROWS_VAR", "PDHG_RES64_NT",
+            "PDHG_UPD_PAIR", "PDHG_UPD_PF")
 
 
 @pytest.fixture(scope="module")
@@ -148,6 +149,63 @@ FP64 = [
 def test_fp64_and_parity_cases(lib, monkeypatch, i):
     env, shape, precision, k, expect = FP64[i]
     _check(lib, monkeypatch, env, shape, expect, precision=precision, k=k)
+
+
+FUSE = {"PDHG_FUSE_RES": "1"}
+# The kernel choices ("<stage>_kernel" family codes of include/pdhg.h, "<stage>_shape" threads): every family of every
+# stage at least once, at the smallest shapes that select it.  (environment, (egno, ndim, nx, ny, T), precision, expected)
+CHOICES = [
+    # x transform of a window: single-role, warp-specialised, batched, DMA, DMA half-real, fp64, generic
+    ({}, (1, 2, 4096, 32, 3), 4, {"xt_kernel": 1, "xt_shape": 512, "fast_xt": 1, "xt_one_row_kernel": 0}),
+    ({"PDHG_XT_WS": "1"}, (1, 2, 4096, 32, 3), 4, {"xt_kernel": 2, "xt_shape": 512, "fast_xt": 2}),
+    ({}, (1, 2, 2048, 32, 4), 4, {"xt_kernel": 3, "xt_shape": 1024, "fast_xt": 3}),
+    ({}, (1, 2, 4096, 32, 4), 4, {"xt_kernel": 4, "xt_shape": 1024, "fast_xt": 4}),
+    ({}, (1, 2, 8192, 32, 4), 4, {"xt_kernel": 5, "xt_shape": 1024, "fast_xt": 5, "half_real": 1}),
+    ({}, (1, 2, 4096, 32, 3), 8, {"xt_kernel": 6, "xt_shape": 512, "fast_xt": 0, "f64_xt": 1, "xt64_dma": 1}),
+    ({}, (1, 2, 15, 17, 3), 4, {"xt_kernel": 7, "res_kernel": 1, "upd_kernel": 1, "dual_kernel": 1, "dual_shape": 256,
+                                "res_fused_kernel": 0, "dual_fused_kernel": 0}),
+    ({}, (1, 2, 15, 17, 3), 12, {"xt_kernel": 7, "res_kernel": 1, "upd_kernel": 2, "dual_kernel": 2}),
+    # one-row windows: the fp32 kernel at the marching defaults' shapes (c3w1, c2w1; "fast_xt" keeps the window
+    # kernel's code), fp64 without and with G16
+    *[({}, (1, 2, n, n, 1), 4, {"xt_one_row_kernel": 8, "xt_one_row_shape": 512, "fast_xt": 1, "xt_kernel": 1})
+      for n in (4096, 2048)],
+    ({}, (1, 2, 1024, 32, 1), 8, {"xt_one_row_kernel": 9, "xt_one_row_shape": 512, "t1_xt64": 1, "t1_g16": 0}),
+    ({}, (1, 2, 2048, 32, 1), 8, {"xt_one_row_kernel": 10, "xt_one_row_shape": 256, "t1_xt64": 1, "t1_g16": 1}),
+    # rows and dual, fp32: fast rows with the LDS sweep, fused, and the row-per-thread sweep on a one-row window
+    ({}, (1, 2, 16, 256, 3), 4, {"res_kernel": 2, "res_shape": 64, "res_fused_kernel": 0, "upd_kernel": 3, "upd_shape": 64,
+                                 "dual_kernel": 5, "dual_shape": 512, "dual_fused_kernel": 0}),
+    (FUSE, (1, 2, 16, 256, 3), 4, {"res_fused_kernel": 4, "res_fused_shape": 64, "dual_fused_kernel": 6,
+                                   "dual_fused_shape": 512, "fused_residual": 1}),
+    ({}, (1, 2, 16, 256, 1), 4, {"dual_kernel": 3, "dual_shape": 64, "dual_one": 1}),
+    # mixed: fast rows at 512 threads, row-per-thread dual
+    ({}, (1, 2, 16, 4096, 3), 12, {"res_kernel": 2, "upd_kernel": 4, "upd_shape": 512, "dual_kernel": 4}),
+    # fp64 rows: 4-row kernels, the one-row update, task pairs, ny = 8192; fused, and PDHG_RES64_NT=1024
+    ({}, (1, 2, 16, 2048, 3), 8, {"res_kernel": 3, "res_shape": 512, "upd_kernel": 5, "upd_shape": 512, "dual_kernel": 5}),
+    ({}, (1, 2, 16, 2048, 1), 8, {"res_kernel": 3, "res_shape": 256, "upd_kernel": 6, "upd_shape": 256, "upd_t1": 2,
+                                  "dual_kernel": 3}),
+    ({"PDHG_UPD_PAIR": "1"}, (1, 2, 16, 2048, 3), 8, {"upd_kernel": 7, "upd_shape": 512, "upd64_pair": 1}),
+    ({}, (1, 2, 8192, 8192, 3), 8, {"upd_kernel": 8, "upd_shape": 512, "res_kernel": 1, "upd8192": 1}),
+    (FUSE, (1, 2, 16, 4096, 3), 8, {"res_fused_kernel": 5, "res_fused_shape": 512, "res64_nt": 512, "dual_fused_kernel": 6}),
+    (dict(FUSE, PDHG_RES64_NT="1024"), (1, 2, 16, 4096, 3), 8, {"res_fused_kernel": 5, "res_fused_shape": 1024,
+                                                                "res64_nt": 1024, "res_shape": 512}),
+    # 1-D: no 2-D stage
+    ({}, (1, 1, 4096, 1, 3), 4, {"xt_kernel": 0, "res_kernel": 0, "upd_kernel": 0, "dual_kernel": 0}),
+]
+FAMILIES = {"xt": range(1, 8), "xt_one_row": (0, 8, 9, 10), "res": range(0, 4), "res_fused": (0, 4, 5), "upd": range(0, 9),
+            "dual": range(0, 6), "dual_fused": (0, 6)}
+
+
+@pytest.mark.parametrize("i", range(len(CHOICES)), ids=["{}-{}x{}T{}p{}".format(i, c[1][2], c[1][3], c[1][4], c[2])
+                                                        for i, c in enumerate(CHOICES)])
+def test_kernel_choices(lib, monkeypatch, i):
+    env, shape, precision, expect = CHOICES[i]
+    _check(lib, monkeypatch, env, shape, expect, precision=precision)
+
+
+def test_kernel_choice_table_reaches_every_family():
+    for stage, codes in FAMILIES.items():
+        seen = {c[3][stage + "_kernel"] for c in CHOICES if stage + "_kernel" in c[3]}
+        assert seen >= set(codes), (stage, sorted(set(codes) - seen))
 
 
 def test_runtime_keys_need_a_context(lib):
