@@ -31,7 +31,8 @@
  * (pdhg_report_state / pdhg_report_rows / pdhg_trajectories), on multi-device contexts (pdhg_multi_report_state /
  * pdhg_multi_report_rows / pdhg_multi_trajectories) and slab by slab on t-slab contexts (pdhg_slab_report /
  * pdhg_slab_report_rows / pdhg_slab_trajectories, chained by the caller: pdhg_amd/slab.py SlabRunner.report);
- * x-slab contexts have neither.
+ * x-slab contexts have neither.  A third pass, the policy check (pdhg_policy_eval: the closed-loop cost of the
+ * controls against phi), runs on single contexts only.
  */
 #ifndef PDHG_MI355X_H
 #define PDHG_MI355X_H
@@ -273,6 +274,60 @@ typedef struct pdhg_traj_opts {
 } pdhg_traj_opts;
 int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
                       double* x_final, double* traj_x, double* traj_alp);
+
+/* ---------------- policy check: closed-loop cost of the resident controls against phi ----------------
+ * Does following the computed feedback alp cost what phi says it costs?  phi row 0 is the terminal cost g, phi row j
+ * the value with j dt to go, and the controls of row j act between phi rows j and j+1.  So for a path started at x0
+ * with the window's T rows to go,
+ *   sum over steps of dt L(alp(x, t))  +  phi_0(x_T)   ~   phi_T(x0)        (in expectation when epsl > 0):
+ * the dynamic-programming identity of the window, a test of phi and alp together along characteristics (the report's
+ * residual norms are local).  It holds window by window in PDHG_multi_step, each window's row 0 being the previous
+ * window's last row.  One read-only device pass; per sample, all in float64 without fma contraction:
+ *   value    = I[phi row T](x0)
+ *   the path is pdhg_trajectories' own: with the same x_init, method, periods, centring and noise (or seed /
+ *              sample_offset) x_final equals its x_final bit for bit;
+ *   step ind = 0 .. T-1 (alp row T-1-ind; control time runs against PDE time), a_k the interpolated control arrays the
+ *              rollout forms and f_k = f(a_k) their velocities:
+ *                l = sum_k keep_k L(a_k),   L(a) = a^2 / 2 (egno 1, 3) or 0 a^2 (egno 2),   summed in array order,
+ *              keep_k the rollout's sign split: f_k >= 0 for arrays 0 and 2, f_k < 0 for arrays 1 and 3 (egno 3 stores
+ *              arrays 0 and 1 only) -- a component the split drops moves nothing and costs nothing;
+ *   running  = 0.0, then running = running + dt * l, step by step;
+ *   terminal = I[phi row 0](x_T) with opts->terminal == 0; 0.0 with opts->terminal == 1, for a caller who chains
+ *              windows (running of the later rows first, started at its x_final) or evaluates g in closed form;
+ *   cost = running + terminal,   gap = cost - value     (gap > 0: the policy costs more than phi promises).
+ * I[row](x) is linear interpolation of a phi row with the rollout's cell location and boundary extension, whatever
+ * `method` the controls use: 2-D bilinear with periodic axes wrapped, the Neumann axis repeating its edge value and
+ * center_x / center_y honoured; 1-D jnp.interp(period = x_period).  phi is read in the type the context stores it
+ * (float in fp32 contexts, double in fp64 and mixed ones) and widened before any arithmetic.
+ * Starts: x_init [n_sample][ndim] (host float64), or NULL for grid starts: every stride_x-th (and stride_y-th) node,
+ * (xs[i stride_x], ys[j stride_y]) at sample index i ceil(ny / stride_y) + j; traj.n_sample is then 0 or that count, no
+ * start array crosses PCIe and the per-sample outputs are a field over the strided grid.  noise as pdhg_trajectories.
+ * Outputs, each optional (NULL: neither allocated nor copied): report; running, terminal, value [n_sample];
+ * x_final [n_sample][ndim].  Statistics: a sample with any of running, terminal, value not finite counts in
+ * n_nonfinite and is left out of every mean and extremum; means divide by n_sample - n_nonfinite; if that is 0 every
+ * double of the report is NaN.  The accumulation has a fixed order (a row of partial sums per 256 samples, numbered
+ * through the whole call, folded after the last staging chunk; no atomics): the report is a pure function of the
+ * inputs, whatever the chunking, and a repeated call returns the same bits.
+ * The call leaves the state, phi_bar, the iteration's buffers, its stop bookkeeping and a captured graph untouched.
+ * Device temporaries (the staging chunks of pdhg_trajectories' budget and 128 bytes per 256 samples) live for the
+ * call only.  Single contexts of pdhg_create (precision 4, 8, 12); t-slab, x-slab and multi-device handles return
+ * PDHG_ERR_UNSUPPORTED, as do the grids pdhg_trajectories refuses.  PDHG_ERR_ARG: null ctx / opts, unknown method, a
+ * period <= 0, terminal not 0 / 1, sample_offset < 0, x_init == NULL with a stride < 1 or with n_sample neither 0 nor
+ * the strided grid's count, x_init != NULL with n_sample < 1, report and every output NULL. */
+typedef struct pdhg_policy_opts {
+  pdhg_traj_opts traj;     /* samples, method, periods, centring, noise stream: as pdhg_trajectories */
+  int terminal;            /* 0: phi row 0 interpolated at x_final, 1: none */
+  int stride_x, stride_y;  /* grid starts (x_init == NULL): every stride-th node; stride_y ignored in 1-D */
+  int reserved0;
+} pdhg_policy_opts;
+typedef struct pdhg_policy_report {
+  long long n_sample, n_nonfinite;            /* non-finite: any of running, terminal, value not finite */
+  double cost_mean, value_mean, running_mean, terminal_mean;
+  double gap_mean, gap_abs_mean, gap_rms, gap_abs_max, gap_lo, gap_hi;   /* over the finite samples */
+} pdhg_policy_report;
+int pdhg_policy_eval(pdhg_ctx* ctx, const pdhg_policy_opts* opts, const double* x_init, const double* noise,
+                     pdhg_policy_report* report, double* running, double* terminal, double* value,
+                     double* x_final);
 
 /* ---------------- solution report: HJ and continuity residual norms of the resident state ----------------
  * Replaces evaluating compute_HJ_residual_1d / _2d (update_fns_in_pdhg.py:49-70) and compute_cont_residual_1d / _2d

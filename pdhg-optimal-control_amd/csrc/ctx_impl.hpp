@@ -30,6 +30,7 @@
 #include "kernels_xt_f64.hpp"
 #include "kernels_traj.hpp"
 #include "kernels_report.hpp"
+#include "kernels_policy.hpp"
 #include "path_plan.hpp"
 
 using namespace pdhg;
@@ -78,6 +79,31 @@ inline pdhg_report report_from_sums(const double* h, long long n_points) {
     const double nan = std::nan("");
     r.hj_l1 = r.hj_l2 = r.hj_max = r.hj_pos_max = r.hj_active_max = r.compl_l1 = nan;
     r.cont_l1 = r.cont_l2 = r.cont_max = r.rho_min = r.rho_max = r.rho_mean = r.phi_min = r.phi_max = nan;
+  }
+  return r;
+}
+
+// pdhg_policy_report from one folded row of the policy check's sums (kernels_policy.hpp) over n_sample samples
+inline pdhg_policy_report policy_from_sums(const double* h, long long n_sample) {
+  pdhg_policy_report r{};
+  r.n_sample = n_sample;
+  r.n_nonfinite = (long long)h[6];
+  const double n = (double)(r.n_sample - r.n_nonfinite);
+  if (n > 0) {
+    r.running_mean = h[0] / n;
+    r.terminal_mean = h[1] / n;
+    r.value_mean = h[2] / n;
+    r.gap_mean = h[3] / n;
+    r.gap_abs_mean = h[4] / n;
+    r.gap_rms = std::sqrt(h[5] / n);
+    r.cost_mean = h[7] / n;
+    r.gap_abs_max = h[8];
+    r.gap_hi = h[9];
+    r.gap_lo = -h[10];
+  } else {
+    const double nan = std::nan("");
+    r.cost_mean = r.value_mean = r.running_mean = r.terminal_mean = nan;
+    r.gap_mean = r.gap_abs_mean = r.gap_rms = r.gap_abs_max = r.gap_lo = r.gap_hi = nan;
   }
   return r;
 }
@@ -1829,6 +1855,105 @@ struct Impl : ImplBase {
                                mc * w_a * sizeof(double), hipMemcpyDeviceToHost, stream));
       HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
     }
+    return PDHG_OK;
+  }
+
+  // ---------------- policy check (kernels_policy.hpp; include/pdhg.h pdhg_policy_eval) ----------------
+  // Read-only on the state, as the report.  The samples are staged like the rollout's: whole workgroups per chunk
+  // within kTrajBudget, in one allocation that also holds the call's table of partial rows (one per workgroup of the
+  // whole call, then the folded row).  A null output takes no bytes; with grid starts no start array exists at all.
+  int policy_eval(const pdhg_policy_opts& po, const double* x_init, const double* noise, pdhg_policy_report* report,
+                  double* running, double* terminal, double* value, double* x_final) {
+    if (slab || xslab)
+      return fail(PDHG_ERR_UNSUPPORTED, "the policy check needs the whole window in one context, not %s context",
+                  slab ? "a t-slab" : "an x-slab");
+    const pdhg_traj_opts& o = po.traj;
+    const int nd = pb.ndim, T = pb.T;
+    size_t n = (size_t)o.n_sample;
+    unsigned long long gny = 1;
+    if (!x_init) {
+      gny = nd == 2 ? (unsigned long long)((pb.ny + po.stride_y - 1) / po.stride_y) : 1;
+      const size_t count = (size_t)((pb.nx + po.stride_x - 1) / po.stride_x) * (size_t)gny;
+      if (o.n_sample != 0 && n != count)
+        return fail(PDHG_ERR_ARG, "n_sample %lld, but the strided grid has %zu starts (n_sample: that or 0)",
+                    o.n_sample, count);
+      n = count;
+    }
+    const size_t nwg = (n + 255) / 256;
+    if (nwg >= (size_t)1 << 31) return fail(PDHG_ERR_ARG, "n_sample %zu is more than 2^31 workgroups of 256", n);
+    int rc;
+    if ((rc = traj_ready(o))) return rc;
+    const bool noisy = pb.epsl > 0;
+    const size_t w_x = (size_t)nd;   // doubles per sample and row
+    const size_t per = sizeof(double) * ((x_init ? w_x : 0) + (x_final ? w_x : 0) +
+                                         (noisy && noise ? (size_t)T * w_x : 0) + (running ? 1 : 0) +
+                                         (terminal ? 1 : 0) + (value ? 1 : 0));
+    size_t m = per ? std::max<size_t>(kTrajBudget / per, 256) / 256 * 256 : nwg * 256;   // whole workgroups per chunk
+    m = std::min(m, n);
+    const size_t table = (nwg + 1) * kNumSums;   // doubles
+    struct Tmp {   // the table and the chunk buffers: one allocation, freed on every way out
+      double* p = nullptr;
+      ~Tmp() { if (p) hipFree(p); }
+    } tmp;
+    if (hipMalloc((void**)&tmp.p, table * sizeof(double) + m * per) != hipSuccess)
+      return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the policy check failed", table * sizeof(double) + m * per);
+    double* d_next = tmp.p + table;
+    auto take = [&](bool on, size_t doubles) {
+      double* q = on ? d_next : nullptr;
+      if (on) d_next += doubles;
+      return q;
+    };
+    double* d_in = take(x_init != nullptr, m * w_x);
+    double* d_out = take(x_final != nullptr, m * w_x);
+    double* d_noise = take(noisy && noise, (size_t)T * m * w_x);
+    double* d_run = take(running != nullptr, m);
+    double* d_term = take(terminal != nullptr, m);
+    double* d_val = take(value != nullptr, m);
+    PolP<R, P> a{};
+    a.t = traj_params(o, noisy ? (noise ? 1 : 2) : 0);
+    a.t.x_in = d_in;
+    a.t.noise = d_noise;
+    a.t.x_out = d_out;
+    a.phi = phi_dev();
+    a.terminal = po.terminal;
+    a.grid_starts = x_init ? 0 : 1;
+    a.stride_x = x_init ? 1 : po.stride_x;
+    a.stride_y = x_init || nd == 1 ? 1 : po.stride_y;
+    a.gny = gny;
+    a.running = d_run;
+    a.term = d_term;
+    a.value = d_val;
+    a.partials = tmp.p;
+    for (size_t c0 = 0; c0 < n; c0 += m) {
+      const size_t mc = std::min(m, n - c0);
+      if (d_in)
+        HIP_TRY(hipMemcpyAsync(d_in, x_init + c0 * w_x, mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
+      for (int j = 0; d_noise && j < T; ++j)
+        HIP_TRY(hipMemcpyAsync(d_noise + (size_t)j * mc * w_x, noise + ((size_t)j * n + c0) * w_x,
+                               mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
+      a.t.n = mc;
+      a.t.s0 = (unsigned long long)o.sample_offset + c0;
+      a.g0 = c0;
+      const dim3 grid((unsigned)((mc + 255) / 256)), block(256);
+      if (nd == 1)
+        rc = with_egno<2>([&](auto E) { return launch(k_policy_1d<R, P, decltype(E)::value>, grid, block, 0, a); });
+      else
+        rc = with_egno<3>([&](auto E) { return launch(k_policy_2d<R, P, decltype(E)::value>, grid, block, 0, a); });
+      if (rc) return rc;
+      const size_t nb = mc * sizeof(double);
+      if (x_final) HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, nb * w_x, hipMemcpyDeviceToHost, stream));
+      if (running) HIP_TRY(hipMemcpyAsync(running + c0, d_run, nb, hipMemcpyDeviceToHost, stream));
+      if (terminal) HIP_TRY(hipMemcpyAsync(terminal + c0, d_term, nb, hipMemcpyDeviceToHost, stream));
+      if (value) HIP_TRY(hipMemcpyAsync(value + c0, d_val, nb, hipMemcpyDeviceToHost, stream));
+      HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
+    }
+    if (!report) return PDHG_OK;
+    double* d_fold = tmp.p + nwg * kNumSums;
+    if ((rc = launch(k_report_finalize, dim3(1), dim3(1024), 0, (const double*)tmp.p, (int)nwg, d_fold))) return rc;
+    double h[kNumSums];
+    HIP_TRY(hipMemcpyAsync(h, d_fold, sizeof(h), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    *report = policy_from_sums(h, (long long)n);
     return PDHG_OK;
   }
 

@@ -354,6 +354,30 @@ int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x
   });
 }
 
+/* ---------------- policy check ---------------- */
+int pdhg_policy_eval(pdhg_ctx* ctx, const pdhg_policy_opts* opts, const double* x_init, const double* noise,
+                     pdhg_policy_report* report, double* running, double* terminal, double* value,
+                     double* x_final) {
+  if (!ctx || !opts) return fail(PDHG_ERR_ARG, "null context or opts");
+  if (reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
+    return fail(PDHG_ERR_UNSUPPORTED, "the policy check needs a single context (pdhg_create), not a multi-device one");
+  const pdhg_traj_opts& o = opts->traj;
+  if (o.method != 0 && o.method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", o.method);
+  if (opts->terminal != 0 && opts->terminal != 1)
+    return fail(PDHG_ERR_ARG, "terminal %d: 0 phi row 0 at x_final or 1 none", opts->terminal);
+  if (o.sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
+  if (x_init && o.n_sample < 1) return fail(PDHG_ERR_ARG, "n_sample must be >= 1 with x_init");
+  if (!x_init && o.n_sample < 0) return fail(PDHG_ERR_ARG, "n_sample must be 0 or the strided grid's count");
+  if (!report && !running && !terminal && !value && !x_final)
+    return fail(PDHG_ERR_ARG, "report and every output are null: nothing to compute");
+  return dispatch(ctx, [&](auto& im) {
+    if (!(o.x_period > 0) || (im.pb.ndim == 2 && !(o.y_period > 0))) return fail(PDHG_ERR_ARG, "periods must be > 0");
+    if (!x_init && (opts->stride_x < 1 || (im.pb.ndim == 2 && opts->stride_y < 1)))
+      return fail(PDHG_ERR_ARG, "grid starts need strides >= 1, not (%d, %d)", opts->stride_x, opts->stride_y);
+    return im.policy_eval(*opts, x_init, noise, report, running, terminal, value, x_final);
+  });
+}
+
 /* ---------------- solution report ---------------- */
 int pdhg_report_state(pdhg_ctx* ctx, pdhg_report* out) {
   if (!ctx || !out) return fail(PDHG_ERR_ARG, "null context or report");

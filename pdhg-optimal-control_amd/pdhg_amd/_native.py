@@ -27,6 +27,8 @@ EXPORTS = (
     "pdhg_device_bytes", "pdhg_path_info", "pdhg_plan_info", "pdhg_profile_enable", "pdhg_profile_query", "pdhg_algorithmic_bytes",
     # closed-loop trajectories from the resident controls
     "pdhg_trajectories",
+    # policy check (closed-loop cost of the resident controls against phi)
+    "pdhg_policy_eval",
     # solution report (HJ / continuity residual norms of the resident state)
     "pdhg_report_state", "pdhg_report_rows",
     # t-slab decomposition (multi-GPU)
@@ -99,10 +101,31 @@ class pdhg_report(ctypes.Structure):
     ]
 
 
+class pdhg_policy_opts(ctypes.Structure):
+    _fields_ = [
+        ("traj", pdhg_traj_opts), ("terminal", ctypes.c_int), ("stride_x", ctypes.c_int), ("stride_y", ctypes.c_int),
+        ("reserved0", ctypes.c_int),
+    ]
+
+
+class pdhg_policy_report(ctypes.Structure):
+    _fields_ = [
+        ("n_sample", ctypes.c_longlong), ("n_nonfinite", ctypes.c_longlong),
+        ("cost_mean", ctypes.c_double), ("value_mean", ctypes.c_double), ("running_mean", ctypes.c_double),
+        ("terminal_mean", ctypes.c_double), ("gap_mean", ctypes.c_double), ("gap_abs_mean", ctypes.c_double),
+        ("gap_rms", ctypes.c_double), ("gap_abs_max", ctypes.c_double), ("gap_lo", ctypes.c_double),
+        ("gap_hi", ctypes.c_double),
+    ]
+
+
 # the fields a report dict carries (PDHGContext.report, pdhg_amd.report.report_from_arrays)
 REPORT_FIELDS = tuple(f for f, _ in pdhg_report._fields_ if f != "reserved0")
 
+# ... and a policy dict (PDHGContext.policy_eval, pdhg_amd.policy.policy_report_from_samples)
+POLICY_FIELDS = tuple(f for f, _ in pdhg_policy_report._fields_)
+
 TRAJ_METHODS = {"linear": 0, "nearest": 1}
+POLICY_TERMINAL = {"phi0": 0, "none": 1}
 
 _lib = None
 
@@ -153,6 +176,8 @@ def load():
         "pdhg_profile_query": ([P, ctypes.c_char_p, dp, ctypes.POINTER(ctypes.c_int)], ctypes.c_int),
         "pdhg_algorithmic_bytes": ([P, ctypes.c_int, ctypes.c_char_p, dp], ctypes.c_int),
         "pdhg_trajectories": ([P, ctypes.POINTER(pdhg_traj_opts), dp, dp, dp, dp, dp], ctypes.c_int),
+        "pdhg_policy_eval": ([P, ctypes.POINTER(pdhg_policy_opts), dp, dp, ctypes.POINTER(pdhg_policy_report),
+                              dp, dp, dp, dp], ctypes.c_int),
         "pdhg_report_state": ([P, ctypes.POINTER(pdhg_report)], ctypes.c_int),
         "pdhg_report_rows": ([P, ctypes.c_int, ctypes.c_int, dp, dp], ctypes.c_int),
         "pdhg_create_slab": ([ctypes.POINTER(pdhg_problem), ctypes.c_int, ctypes.c_int, ctypes.c_int,

@@ -51,6 +51,43 @@ def traj_arguments(ndim, T, x_init, method, x_period, y_period=None, center=(Fal
     return o, x0.reshape(n, ndim), noise, "x" in record, "alp" in record
 
 
+POLICY_OUTPUTS = ("running", "terminal", "value", "x_final")
+
+
+def policy_arguments(ndim, T, nx, ny, x_init, stride, method, x_period, y_period=None, center=(False, False),
+                     noise=None, seed=0, sample_offset=0, terminal="phi0", outputs=("running", "terminal", "value")):
+    """Checked arguments of PDHGContext.policy_eval, before any native call: (options struct, x_init [n, ndim] or None
+    for grid starts, noise [T, n, ndim] or None, n, the outputs asked for).  Raises ValueError on a shape or value the
+    library would refuse, with the shapes spelled out."""
+    if terminal not in N.POLICY_TERMINAL:
+        raise ValueError("terminal must be 'phi0' or 'none', not {!r}".format(terminal))
+    outputs = (outputs,) if isinstance(outputs, str) else tuple(outputs or ())
+    if set(outputs) - set(POLICY_OUTPUTS):
+        raise ValueError("outputs takes {}, not {!r}".format(" / ".join(POLICY_OUTPUTS), outputs))
+    po = N.pdhg_policy_opts()
+    po.terminal = N.POLICY_TERMINAL[terminal]
+    if x_init is None:
+        if stride is None:
+            raise ValueError("give x_init [n_sample{}] or a stride for grid starts".format("" if ndim == 1 else ", 2"))
+        st = (stride,) * ndim if np.ndim(stride) == 0 else tuple(stride)
+        if len(st) != ndim or any(int(v) != v or v < 1 for v in st):
+            raise ValueError("stride must be {} integer(s) >= 1, not {!r}".format(ndim, stride))
+        st = tuple(int(v) for v in st)
+        n = -(-nx // st[0]) * (-(-ny // st[1]) if ndim == 2 else 1)
+        # the rollout's own checks, on a start array of the right length that is never uploaded
+        x_chk = np.zeros((n,) + (() if ndim == 1 else (2,)))
+        po.stride_x, po.stride_y = st[0], st[1] if ndim == 2 else 1
+    else:
+        if stride is not None:
+            raise ValueError("stride selects grid starts: it cannot be combined with x_init")
+        x_chk = x_init
+        po.stride_x = po.stride_y = 1
+    o, x0, noise, _, _ = traj_arguments(ndim, T, x_chk, method, x_period, y_period, center, noise, (), seed,
+                                        sample_offset)
+    po.traj = o
+    return po, (None if x_init is None else x0), noise, x0.shape[0], outputs
+
+
 class PDHGContext:
     def __init__(self, egno, ndim, nx, ny, T, dx, dy, dt, xs, ys=None, epsl=0.0, c_on_rho=70.0, bc=None,
                  C=1.0, pow=1.0, Ct=1.0, precision="fp32", rho_alp_iters=1, device=0):
@@ -201,6 +238,28 @@ class PDHGContext:
         N.check(self._lib.pdhg_trajectories(self._h, ctypes.byref(o), N.dptr(x0), N.dptr(noise), N.dptr(x_final),
                                             N.dptr(traj_x), N.dptr(traj_alp)))
         return traj_alp, traj_x, x_final
+
+    def policy_eval(self, x_init=None, stride=None, method="linear", x_period=2.0, y_period=None,
+                    center=(False, False), noise=None, seed=0, sample_offset=0, terminal="phi0",
+                    outputs=("running", "terminal", "value")):
+        """The policy check (pdhg_policy_eval): the closed-loop cost of the resident controls against phi.  Per sample
+        value = phi row T at the start, running = sum dt L(alp) along trajectories()' own path, terminal = phi row 0
+        at its end (terminal="none": 0.0, for chaining windows); gap = running + terminal - value.  Starts: x_init
+        [n(, 2)], or stride (an int, or a pair in 2-D) for every stride-th grid node, sample index
+        i * ceil(ny / stride_y) + j, with nothing uploaded.  phi is interpolated linearly whatever `method` the
+        controls use.  Returns a dict: pdhg_policy_report's fields, the per-sample arrays named in `outputs` ([n]) and
+        x_final [n(, 2)] when "x_final" is among them.  One read-only device pass."""
+        po, x0, noise, n, outputs = policy_arguments(self.ndim, self.T, self.nx, self.ny, x_init, stride, method,
+                                                     x_period, y_period, center, noise, seed, sample_offset,
+                                                     terminal, outputs)
+        arr = {k: np.empty((n,) + ((2,) if k == "x_final" and self.ndim == 2 else ())) for k in outputs}
+        r = N.pdhg_policy_report()
+        N.check(self._lib.pdhg_policy_eval(self._h, ctypes.byref(po), N.dptr(x0), N.dptr(noise), ctypes.byref(r),
+                                           N.dptr(arr.get("running")), N.dptr(arr.get("terminal")),
+                                           N.dptr(arr.get("value")), N.dptr(arr.get("x_final"))))
+        d = {f: getattr(r, f) for f in N.POLICY_FIELDS}
+        d.update(arr)
+        return d
 
     # ---- how good is the state the context holds ----
     def report(self):

@@ -19,7 +19,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-from .context import traj_arguments
+from .context import policy_arguments, traj_arguments
 
 
 class MultiContext:
@@ -125,6 +125,18 @@ class MultiContext:
         N.check(self._lib.pdhg_multi_trajectories(self._h, ctypes.byref(o), N.dptr(x0), N.dptr(noise),
                                                   N.dptr(x_final), N.dptr(traj_x), N.dptr(traj_alp)))
         return traj_alp, traj_x, x_final
+
+    def policy_eval(self, x_init=None, stride=None, method="linear", x_period=2.0, y_period=None,
+                    center=(False, False), noise=None, seed=0, sample_offset=0, terminal="phi0",
+                    outputs=("running", "terminal", "value")):
+        """PDHGContext.policy_eval's signature; the policy check runs on single contexts only, so after the argument
+        checks the library refuses this handle (PDHGUnsupported)."""
+        po, x0, noise, _, _ = policy_arguments(2, self.T, self.nx, self.ny, x_init, stride, method, x_period, y_period,
+                                               center, noise, seed, sample_offset, terminal, outputs)
+        r = N.pdhg_policy_report()
+        N.check(self._lib.pdhg_policy_eval(self._h, ctypes.byref(po), N.dptr(x0), N.dptr(noise), ctypes.byref(r),
+                                           None, None, None, None))
+        raise AssertionError("pdhg_policy_eval accepted a multi-device handle")
 
     def set_stop_rules(self, converge=True, nan=True):
         N.check(self._lib.pdhg_multi_set_stop_rules(self._h, 1 if converge else 0, 1 if nan else 0))

@@ -13,7 +13,9 @@ and saves them as traj_<prefix>.npz (+ figures).  --tfboard is accepted and igno
 Extra flags: --precision {fp32,fp64,mixed}, --rho_alp_iters (the reference fixes 10), --out (root dir),
 --load_middle / --load_middle_timestamp (resume from middle results, run_example.py:246-248), --report (after
 every window one device pass over its final state: the HJ and continuity residual norms, pdhg_amd.report; the
-window with the largest HJ residual and the last one are printed).
+window with the largest HJ residual and the last one are printed), --policy_check [N] (after every window the policy
+check of its final state from N trajectory starts, default --plot_traj_num_1d: the closed-loop cost of alp against phi,
+pdhg_amd.policy; the window with the largest gap and the last one are printed).
 """
 import argparse
 import os
@@ -67,6 +69,9 @@ def build_parser():
     A("--out", default=".")
     A("--report", type=int, nargs="?", const=1, default=0,
       help="print the residual norms of the worst and the last window (--report or --report 1)")
+    A("--policy_check", type=int, nargs="?", const=-1, default=0,
+      help="print the closed-loop cost of alp against phi for the worst and the last window, from N trajectory "
+           "starts (--policy_check alone: N = --plot_traj_num_1d)")
     return ap
 
 
@@ -84,8 +89,8 @@ def make_grid(ndim, egno, nx, ny, nt, x_period, y_period, T):
 def solve_HJ(ndim, n_ctrl, egno, epsl, fns_dict, nx, ny, nt, x_period, y_period, T, x_arr, c_on_rho,
              time_step_per_PDHG, stepsz_param, N_maxiter, print_freq, eps, bc, C=1.0, pow=1.0, Ct=1.0,
              rho_alp_iters=10, precision="fp64", save_middle_dir=None, save_middle_prefix=None, load_middle_dir=None,
-             load_middle_prefix=None, verbose=True, stats=None, report=False):
-    """run_example.py:157-210 with the device-resident update functions.  stats / report: PDHG_multi_step's."""
+             load_middle_prefix=None, verbose=True, stats=None, report=False, policy=None):
+    """run_example.py:157-210 with the device-resident update functions.  stats / report / policy: PDHG_multi_step's."""
     dt = T / (nt - 1)
     dx, dy = x_period / nx, y_period / ny
     if ndim == 1:
@@ -102,7 +107,7 @@ def solve_HJ(ndim, n_ctrl, egno, epsl, fns_dict, nx, ny, nt, x_period, y_period,
                                              print_freq=print_freq, eps=eps, save_middle_dir=save_middle_dir,
                                              save_middle_prefix=save_middle_prefix, load_middle_dir=load_middle_dir,
                                              load_middle_prefix=load_middle_prefix, verbose=verbose, stats=stats,
-                                             report=report)
+                                             report=report, policy=policy)
 
 
 def main(argv=None):
@@ -115,6 +120,10 @@ def main(argv=None):
         n_ctrl, bc = 1, (1, 0)
     else:
         n_ctrl, bc = F.ndim, (0 if F.ndim == 1 else (0, 0))
+    n_pol = F.plot_traj_num_1d if F.policy_check < 0 else F.policy_check
+    if F.policy_check and n_pol < 1:
+        raise SystemExit("--policy_check needs N >= 1 starts (--policy_check N, or --plot_traj_num_1d N)")
+    policy = {"n": n_pol, "x_period": F.x_period, "y_period": F.y_period} if F.policy_check else None
     prefix = "nt{}_nx{}".format(F.nt, F.nx) if F.ndim == 1 else "nt{}_nx{}_ny{}".format(F.nt, F.nx, F.ny)
     if F.load:
         stamp = F.load_timestamp
@@ -141,7 +150,7 @@ def main(argv=None):
                                      save_middle_prefix=prefix if F.save_middle else None,
                                      load_middle_dir=save_dir if F.load_middle else None,
                                      load_middle_prefix=prefix if F.load_middle else None, stats=stats,
-                                     report=bool(F.report))
+                                     report=bool(F.report), policy=policy)
         if F.save:
             solver.save(save_dir, prefix, (results, errs_all))
     iters, phi = results[-1][0], results[-1][1]
@@ -151,6 +160,13 @@ def main(argv=None):
         worst = max(reps, key=lambda r: r[1]["hj_max"] if r[1]["hj_max"] == r[1]["hj_max"] else float("inf"))
         print("report, worst window (solve {}): {}".format(worst[0], format_report(worst[1])), flush=True)
         print("report, last window (solve {}): {}".format(reps[-1][0], format_report(reps[-1][1])), flush=True)
+    pols = [(i, s["policy"]) for i, s in enumerate(stats) if "policy" in s]
+    if pols:
+        from .policy import format_policy
+        worst = max(pols, key=lambda r: r[1]["gap_abs_max"] if r[1]["gap_abs_max"] == r[1]["gap_abs_max"]
+                    else float("inf"))
+        print("policy check, worst window (solve {}): {}".format(worst[0], format_policy(worst[1])), flush=True)
+        print("policy check, last window (solve {}): {}".format(pols[-1][0], format_policy(pols[-1][1])), flush=True)
     if F.plot:
         plot_results(F, results, x_arr, t_arr, fns, bc, n_ctrl, plot_dir, prefix)
     print("windows: {}  last window iterations: {}  phi shape: {}  saved: {}".format(

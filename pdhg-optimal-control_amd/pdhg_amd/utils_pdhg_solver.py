@@ -42,10 +42,12 @@ def _native_tag(fp, fd):
 
 
 def _device_oneiter(tag, fns_dict, phi0, rho0, alp0, x_arr, ndim, dt, dspatial, c_on_rho, epsl, stepsz_param,
-                    N_maxiter, print_freq, eps, verbose, stats, last_only=False, report=False):
+                    N_maxiter, print_freq, eps, verbose, stats, last_only=False, report=False, policy=None):
     """last_only (PDHG_multi_step, which reads results_all[-1] only, utils_pdhg_solver.py:187): the print-point
     records keep no state copies (they would be discarded).  report: the window's stats entry gains "report", the
-    residual norms of the state it ended in (PDHGContext.report)."""
+    residual norms of the state it ended in (PDHGContext.report).  policy (a dict n, x_period, y_period[, seed]): the
+    entry gains "policy", the closed-loop cost of the window's controls against its phi from run_example's n trajectory
+    starts (pdhg_amd.policy.run_policy_check)."""
     spec = U._spec(fns_dict)
     phi0 = np.asarray(phi0, dtype=np.float64)
     T = phi0.shape[0] - 1
@@ -104,6 +106,10 @@ def _device_oneiter(tag, fns_dict, phi0, rho0, alp0, x_arr, ndim, dt, dspatial, 
         stats.append(dict(last, window_iters=i + 1))   # + the iterations this window ran
         if report:
             stats[-1]["report"] = ctx.report()
+        if policy:
+            from .policy import run_policy_check
+            stats[-1]["policy"] = run_policy_check(ctx, spec["egno"], ndim, policy["x_period"], policy.get("y_period"),
+                                                   epsl, policy["n"], seed=policy.get("seed", 0))
     phi, rho, alp = ctx.get_state()
     # rho / alp as the device holds them: read-only (the reference returns immutable jax arrays), so the next window's
     # set_state can keep them on the device when they come back unchanged (PDHG_multi_step: rho0, alp0 = rho_c, alp_c)
@@ -118,17 +124,20 @@ def _device_oneiter(tag, fns_dict, phi0, rho0, alp0, x_arr, ndim, dt, dspatial, 
 
 def PDHG_solver_oneiter(fn_update_primal, fn_update_dual, fns_dict, phi0, rho0, alp0, x_arr, t_arr, ndim, dt, dspatial,
                         c_on_rho, epsl=0.0, stepsz_param=0.9, fv=None, N_maxiter=1000000, print_freq=1000, eps=1e-6,
-                        tfboard=False, tfrecord_ind=0, verbose=True, stats=None, _last_only=False, report=False):
+                        tfboard=False, tfrecord_ind=0, verbose=True, stats=None, _last_only=False, report=False,
+                        policy=None):
     """Outer PDHG loop (utils_pdhg_solver.py:9-94).  Returns (results_all, error_all).  _last_only (internal, used by
     PDHG_multi_step): the print-point entries of results_all carry no state (only results_all[-1] is read there).
     report=True (device loop, with a stats list): the appended stats entry gains "report", the KKT residual norms of
-    the final state from one device pass (PDHGContext.report); the default path is unchanged."""
+    the final state from one device pass (PDHGContext.report); policy (a dict n, x_period, y_period[, seed]; device
+    loop, with a stats list): the entry gains "policy", the policy check of the final state from n trajectory starts
+    (PDHGContext.policy_eval).  The default path is unchanged."""
     tag = _native_tag(fn_update_primal, fn_update_dual)
     if tag is not None:
         U.check_fv(fv, ndim, np.shape(phi0)[1:], dspatial, tag["bc"])
         return _device_oneiter(tag, fns_dict, phi0, rho0, alp0, x_arr, ndim, dt, dspatial, c_on_rho, epsl,
                                stepsz_param, N_maxiter, print_freq, eps, verbose, stats, last_only=_last_only,
-                               report=report)
+                               report=report, policy=policy)
     # generic callables: the reference's host loop, one device call per update
     phi_prev, rho_prev, alp_prev = phi0, rho0, alp0
     tau, sigma = stepsz_param / 1.5, stepsz_param * 1.5
@@ -175,9 +184,10 @@ def _stacked(alp):
 def PDHG_multi_step(fn_update_primal, fn_update_dual, fns_dict, g, x_arr, ndim, nt, nspatial, dt, dspatial, c_on_rho,
                     time_step_per_PDHG=2, epsl=0.0, stepsz_param=0.9, n_ctrl=None, fv=None, N_maxiter=1000000,
                     print_freq=1000, eps=1e-6, tfboard=False, save_middle_dir=None, save_middle_prefix=None,
-                    load_middle_dir=None, load_middle_prefix=None, verbose=True, stats=None, report=False):
-    """Time-window marching with NaN step-size back-off (utils_pdhg_solver.py:97-225).  report=True: every window's
-    stats entry gains "report" (PDHG_solver_oneiter)."""
+                    load_middle_dir=None, load_middle_prefix=None, verbose=True, stats=None, report=False,
+                    policy=None):
+    """Time-window marching with NaN step-size back-off (utils_pdhg_solver.py:97-225).  report=True / policy=dict:
+    every window's stats entry gains "report" / "policy" (PDHG_solver_oneiter)."""
     from .solver import load_middle_solution
     if n_ctrl is None:
         n_ctrl = ndim
@@ -243,7 +253,7 @@ def PDHG_multi_step(fn_update_primal, fn_update_dual, fns_dict, g, x_arr, ndim, 
                                                     x_arr, t_arr, ndim, dt, dspatial, c_on_rho, epsl=epsl,
                                                     stepsz_param=stepsz_param, fv=fv, N_maxiter=N_maxiter,
                                                     print_freq=print_freq, eps=eps, verbose=verbose, stats=stats,
-                                                    _last_only=True, report=report)
+                                                    _last_only=True, report=report, policy=policy)
             if np.any(np.isnan(errs)):
                 if stepsz_param > s_min + s_delta:            # back-off, utils_pdhg_solver.py:180-183
                     stepsz_param -= s_delta
