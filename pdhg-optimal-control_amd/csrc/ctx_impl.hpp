@@ -1721,10 +1721,42 @@ struct Impl : ImplBase {
   }
 
   // ---------------- closed-loop trajectories (kernels_traj.hpp; include/pdhg.h pdhg_trajectories) ----------------
-  // Samples are staged in chunks: the device temporaries (positions in / out, the chunk's noise and records) stay
-  // within kTrajBudget however many samples and rows the call has.  A chunk's rows are contiguous runs of the
-  // host arrays [step][n][...], copied row by row.
+  // Samples are staged in chunks of whole workgroups out of one allocation: the device temporaries (positions in /
+  // out, the chunk's noise, records or per-sample outputs) stay within kTrajBudget however many samples and rows the
+  // call has.  `lead` doubles come first (the policy check's partial table), then a chunk's buffers, carved by take().
   static constexpr size_t kTrajBudget = (size_t)64 << 20;
+  struct SampleChunks {
+    size_t n;                 // samples of the call
+    hipStream_t stream;
+    size_t m = 0;             // samples per chunk: a multiple of 256, or n
+    double* base = nullptr;   // freed on every way out
+    double* next = nullptr;
+    ~SampleChunks() { if (base) hipFree(base); }
+    // per: bytes a sample takes in the chunk buffers; 0 (grid starts with the report only): the call is one chunk
+    int alloc(size_t per, size_t lead, const char* what) {
+      m = std::min(n, per ? std::max<size_t>(kTrajBudget / per, 256) / 256 * 256 : n);
+      const size_t bytes = lead * sizeof(double) + m * per;
+      if (hipMalloc((void**)&base, bytes) != hipSuccess)
+        return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the %s failed", bytes, what);
+      next = base + lead;
+      return PDHG_OK;
+    }
+    double* take(bool on, size_t doubles) { return on ? std::exchange(next, next + doubles) : nullptr; }
+    // rows [j][c0 .. c0 + mc) of a host array [rows][n][w] into the dense device array [rows][mc][w], and back; an
+    // array that is not there (null on either side) moves nothing.  d is take()'s, const only in the argument block.
+    int up(const double* d, const double* h, int rows, size_t c0, size_t mc, size_t w) const {
+      for (int j = 0; d && h && j < rows; ++j)
+        HIP_TRY(hipMemcpyAsync(const_cast<double*>(d) + (size_t)j * mc * w, h + ((size_t)j * n + c0) * w,
+                               mc * w * sizeof(double), hipMemcpyHostToDevice, stream));
+      return PDHG_OK;
+    }
+    int down(double* h, const double* d, int rows, size_t c0, size_t mc, size_t w) const {
+      for (int j = 0; d && h && j < rows; ++j)
+        HIP_TRY(hipMemcpyAsync(h + ((size_t)j * n + c0) * w, d + (size_t)j * mc * w, mc * w * sizeof(double),
+                               hipMemcpyDeviceToHost, stream));
+      return PDHG_OK;
+    }
+  };
   std::vector<double> grid_x, grid_y;   // the grid coordinates in fp64 (kp.ax / kp.ay hold f coefficients in R)
   double* d_xs64 = nullptr;             // ... on the device, uploaded by the first call
   double* d_ys64 = nullptr;
@@ -1813,55 +1845,38 @@ struct Impl : ImplBase {
     const size_t w_x = (size_t)nd, w_a = (size_t)nc;   // doubles per sample and row
     const size_t per = sizeof(double) * (2 * w_x + (noisy && noise ? (size_t)T * w_x : 0) +
                                          (traj_x ? (size_t)(T + 1) * w_x : 0) + (traj_alp ? (size_t)T * w_a : 0));
-    size_t m = std::max<size_t>(kTrajBudget / per, 256) / 256 * 256;   // whole workgroups per chunk
-    m = std::min(m, n);
-    struct Tmp {   // the chunk buffers: one allocation, freed on every way out
-      double* p = nullptr;
-      ~Tmp() { if (p) hipFree(p); }
-    } tmp;
-    if (hipMalloc((void**)&tmp.p, m * per) != hipSuccess)
-      return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the trajectory chunk failed", m * per);
-    double* d_in = tmp.p;
-    double* d_out = d_in + m * w_x;
-    double* d_next = d_out + m * w_x;
-    double* d_noise = nullptr;
-    double* d_rx = nullptr;
-    double* d_ra = nullptr;
-    if (noisy && noise) d_noise = d_next, d_next += (size_t)T * m * w_x;
-    if (traj_x) d_rx = d_next, d_next += (size_t)(T + 1) * m * w_x;
-    if (traj_alp) d_ra = d_next;
+    SampleChunks st{n, stream};
+    if ((rc = st.alloc(per, 0, "trajectory chunk"))) return rc;
     TrajP<R> a = traj_params(o, noisy ? (noise ? 1 : 2) : 0);
-    a.x_in = d_in;
-    a.noise = d_noise;
-    a.x_out = d_out;
-    a.rec_x = d_rx;
-    a.rec_a = d_ra;
-    for (size_t c0 = 0; c0 < n; c0 += m) {
-      const size_t mc = std::min(m, n - c0);
-      HIP_TRY(hipMemcpyAsync(d_in, x_init + c0 * w_x, mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
-      for (int j = 0; d_noise && j < T; ++j)
-        HIP_TRY(hipMemcpyAsync(d_noise + (size_t)j * mc * w_x, noise + ((size_t)j * n + c0) * w_x,
-                               mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
+    a.x_in = st.take(true, st.m * w_x);
+    a.x_out = st.take(true, st.m * w_x);
+    a.noise = st.take(noisy && noise, (size_t)T * st.m * w_x);
+    a.rec_x = st.take(traj_x != nullptr, (size_t)(T + 1) * st.m * w_x);
+    a.rec_a = st.take(traj_alp != nullptr, (size_t)T * st.m * w_a);
+    for (size_t c0 = 0; c0 < n; c0 += st.m) {
+      const size_t mc = std::min(st.m, n - c0);
+      if ((rc = st.up(a.x_in, x_init, 1, c0, mc, w_x)) || (rc = st.up(a.noise, noise, T, c0, mc, w_x))) return rc;
       a.n = mc;
       a.s0 = (unsigned long long)o.sample_offset + c0;
       if ((rc = launch_traj(a))) return rc;
-      if (x_final)
-        HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, mc * w_x * sizeof(double), hipMemcpyDeviceToHost, stream));
-      for (int j = 0; d_rx && j <= T; ++j)
-        HIP_TRY(hipMemcpyAsync(traj_x + ((size_t)j * n + c0) * w_x, d_rx + (size_t)j * mc * w_x,
-                               mc * w_x * sizeof(double), hipMemcpyDeviceToHost, stream));
-      for (int j = 0; d_ra && j < T; ++j)
-        HIP_TRY(hipMemcpyAsync(traj_alp + ((size_t)j * n + c0) * w_a, d_ra + (size_t)j * mc * w_a,
-                               mc * w_a * sizeof(double), hipMemcpyDeviceToHost, stream));
+      if ((rc = st.down(x_final, a.x_out, 1, c0, mc, w_x)) || (rc = st.down(traj_x, a.rec_x, T + 1, c0, mc, w_x)) ||
+          (rc = st.down(traj_alp, a.rec_a, T, c0, mc, w_a)))
+        return rc;
       HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
     }
     return PDHG_OK;
   }
 
   // ---------------- policy check (kernels_policy.hpp; include/pdhg.h pdhg_policy_eval) ----------------
-  // Read-only on the state, as the report.  The samples are staged like the rollout's: whole workgroups per chunk
-  // within kTrajBudget, in one allocation that also holds the call's table of partial rows (one per workgroup of the
-  // whole call, then the folded row).  A null output takes no bytes; with grid starts no start array exists at all.
+  // Read-only on the state, as the report.  The samples are staged like the rollout's, in one allocation that also
+  // holds the call's table of partial rows (one per workgroup of the whole call, then the folded row).  A null output
+  // takes no bytes; with grid starts no start array exists at all.
+  int launch_policy(const PolP<R, P>& a) {
+    const dim3 grid((unsigned)((a.t.n + 255) / 256)), block(256);
+    if (pb.ndim == 1)
+      return with_egno<2>([&](auto E) { return launch(k_policy_1d<R, P, decltype(E)::value>, grid, block, 0, a); });
+    return with_egno<3>([&](auto E) { return launch(k_policy_2d<R, P, decltype(E)::value>, grid, block, 0, a); });
+  }
   int policy_eval(const pdhg_policy_opts& po, const double* x_init, const double* noise, pdhg_policy_report* report,
                   double* running, double* terminal, double* value, double* x_final) {
     if (slab || xslab)
@@ -1888,68 +1903,38 @@ struct Impl : ImplBase {
     const size_t per = sizeof(double) * ((x_init ? w_x : 0) + (x_final ? w_x : 0) +
                                          (noisy && noise ? (size_t)T * w_x : 0) + (running ? 1 : 0) +
                                          (terminal ? 1 : 0) + (value ? 1 : 0));
-    size_t m = per ? std::max<size_t>(kTrajBudget / per, 256) / 256 * 256 : nwg * 256;   // whole workgroups per chunk
-    m = std::min(m, n);
-    const size_t table = (nwg + 1) * kNumSums;   // doubles
-    struct Tmp {   // the table and the chunk buffers: one allocation, freed on every way out
-      double* p = nullptr;
-      ~Tmp() { if (p) hipFree(p); }
-    } tmp;
-    if (hipMalloc((void**)&tmp.p, table * sizeof(double) + m * per) != hipSuccess)
-      return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the policy check failed", table * sizeof(double) + m * per);
-    double* d_next = tmp.p + table;
-    auto take = [&](bool on, size_t doubles) {
-      double* q = on ? d_next : nullptr;
-      if (on) d_next += doubles;
-      return q;
-    };
-    double* d_in = take(x_init != nullptr, m * w_x);
-    double* d_out = take(x_final != nullptr, m * w_x);
-    double* d_noise = take(noisy && noise, (size_t)T * m * w_x);
-    double* d_run = take(running != nullptr, m);
-    double* d_term = take(terminal != nullptr, m);
-    double* d_val = take(value != nullptr, m);
+    SampleChunks st{n, stream};
+    if ((rc = st.alloc(per, (nwg + 1) * kNumSums, "policy check"))) return rc;
     PolP<R, P> a{};
     a.t = traj_params(o, noisy ? (noise ? 1 : 2) : 0);
-    a.t.x_in = d_in;
-    a.t.noise = d_noise;
-    a.t.x_out = d_out;
+    a.t.x_in = st.take(x_init != nullptr, st.m * w_x);
+    a.t.x_out = st.take(x_final != nullptr, st.m * w_x);
+    a.t.noise = st.take(noisy && noise, (size_t)T * st.m * w_x);
     a.phi = phi_dev();
     a.terminal = po.terminal;
     a.grid_starts = x_init ? 0 : 1;
     a.stride_x = x_init ? 1 : po.stride_x;
     a.stride_y = x_init || nd == 1 ? 1 : po.stride_y;
     a.gny = gny;
-    a.running = d_run;
-    a.term = d_term;
-    a.value = d_val;
-    a.partials = tmp.p;
-    for (size_t c0 = 0; c0 < n; c0 += m) {
-      const size_t mc = std::min(m, n - c0);
-      if (d_in)
-        HIP_TRY(hipMemcpyAsync(d_in, x_init + c0 * w_x, mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
-      for (int j = 0; d_noise && j < T; ++j)
-        HIP_TRY(hipMemcpyAsync(d_noise + (size_t)j * mc * w_x, noise + ((size_t)j * n + c0) * w_x,
-                               mc * w_x * sizeof(double), hipMemcpyHostToDevice, stream));
+    a.running = st.take(running != nullptr, st.m);
+    a.term = st.take(terminal != nullptr, st.m);
+    a.value = st.take(value != nullptr, st.m);
+    a.partials = st.base;
+    for (size_t c0 = 0; c0 < n; c0 += st.m) {
+      const size_t mc = std::min(st.m, n - c0);
+      if ((rc = st.up(a.t.x_in, x_init, 1, c0, mc, w_x)) || (rc = st.up(a.t.noise, noise, T, c0, mc, w_x))) return rc;
       a.t.n = mc;
       a.t.s0 = (unsigned long long)o.sample_offset + c0;
       a.g0 = c0;
-      const dim3 grid((unsigned)((mc + 255) / 256)), block(256);
-      if (nd == 1)
-        rc = with_egno<2>([&](auto E) { return launch(k_policy_1d<R, P, decltype(E)::value>, grid, block, 0, a); });
-      else
-        rc = with_egno<3>([&](auto E) { return launch(k_policy_2d<R, P, decltype(E)::value>, grid, block, 0, a); });
-      if (rc) return rc;
-      const size_t nb = mc * sizeof(double);
-      if (x_final) HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, nb * w_x, hipMemcpyDeviceToHost, stream));
-      if (running) HIP_TRY(hipMemcpyAsync(running + c0, d_run, nb, hipMemcpyDeviceToHost, stream));
-      if (terminal) HIP_TRY(hipMemcpyAsync(terminal + c0, d_term, nb, hipMemcpyDeviceToHost, stream));
-      if (value) HIP_TRY(hipMemcpyAsync(value + c0, d_val, nb, hipMemcpyDeviceToHost, stream));
+      if ((rc = launch_policy(a))) return rc;
+      if ((rc = st.down(x_final, a.t.x_out, 1, c0, mc, w_x)) || (rc = st.down(running, a.running, 1, c0, mc, 1)) ||
+          (rc = st.down(terminal, a.term, 1, c0, mc, 1)) || (rc = st.down(value, a.value, 1, c0, mc, 1)))
+        return rc;
       HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
     }
     if (!report) return PDHG_OK;
-    double* d_fold = tmp.p + nwg * kNumSums;
-    if ((rc = launch(k_report_finalize, dim3(1), dim3(1024), 0, (const double*)tmp.p, (int)nwg, d_fold))) return rc;
+    double* d_fold = st.base + nwg * kNumSums;
+    if ((rc = launch(k_report_finalize, dim3(1), dim3(1024), 0, (const double*)st.base, (int)nwg, d_fold))) return rc;
     double h[kNumSums];
     HIP_TRY(hipMemcpyAsync(h, d_fold, sizeof(h), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));

@@ -9,6 +9,13 @@
 // f) must fall as they do on the host, so the position arithmetic is compiled without fma contraction and in the
 // oracle's operation order.
 //
+// One time step is one function, traj_step_1d / traj_step_2d, called by the rollout and by the policy check
+// (kernels_policy.hpp): their paths are the same bits by construction.  Two things keep the bits when this text is
+// edited.  `#pragma clang fp contract(off)` is lexical: every helper carries it in its own body, or the compiler may
+// fuse across its statements.  And the build has no fast-math, so with contraction off an fp64 result is fixed by its
+// expression tree, not by scheduling or registers: keep the operand order of the weights and sums, and widen R / P to
+// double before any arithmetic.  The generated code may change; the results may not.
+//
 // Noise: a staged array of standard normals [T][n][ndim], or Philox4x32-10 + Box-Muller on the device:
 //   key     = (seed low word, seed high word)
 //   counter = (sample low word, sample high word, step, axis pair)        sample = global sample index
@@ -133,8 +140,130 @@ __device__ __forceinline__ TrajCell traj_locate(double x, const double* __restri
   return c;
 }
 
-// 2-D: alp arrays 0, 1 drive x (a1x for f >= 0, a2x for f < 0), arrays 2, 3 drive y; egno 3 stores 0 and 1 only
-// (f = (alp, x), set_fns.py:98).  Records are [step][sample][...]: a wave's stores are contiguous.
+// Bilinear value on two cells from the corners v = (00, 10, 01, 11), first index x: the four weights and the sum in
+// this operand order, corners widened before any arithmetic.  Callers load every corner (of every array) first.
+template <typename V>
+__device__ __forceinline__ double traj_bilinear(const TrajCell& cx, const TrajCell& cy, const V (&v)[4]) {
+#pragma clang fp contract(off)
+  const double u = cx.u, w = cy.u;
+  const double w00 = (1.0 - u) * (1.0 - w), w10 = u * (1.0 - w), w01 = (1.0 - u) * w, w11 = u * w;
+  return w00 * (double)v[0] + w10 * (double)v[1] + w01 * (double)v[2] + w11 * (double)v[3];
+}
+
+// 1-D linear cell of xm = x mod P (jnp.interp(period=P), run_example.py:18-52): the cell before node 0 (from the last
+// node of the previous period) and after node n-1 (to node 0 of the next) closes the period; u is the weight of j1
+__device__ __forceinline__ TrajCell traj_cell_1d(double xm, const double* __restrict__ g, int n, double P,
+                                                 double inv_h) {
+#pragma clang fp contract(off)
+  int j = (int)fmin(fmax((xm - g[0]) * inv_h, 0.0), (double)(n - 1));
+  while (j > 0 && xm < g[j]) --j;
+  while (j < n - 1 && xm > g[j + 1]) ++j;
+  const bool before = xm < g[0], after = j + 1 >= n;
+  const double lo = before ? g[n - 1] - P : g[j];
+  const double hi = before ? g[0] : after ? g[0] + P : g[j + 1];
+  TrajCell c;
+  c.j0 = before ? n - 1 : j;
+  c.j1 = before || after ? 0 : j + 1;
+  c.u = hi > lo ? (xm - lo) / (hi - lo) : 0.0;
+  return c;
+}
+
+// ---- one time step of one sample: the only text of the marching arithmetic (k_traj_*, k_policy_*) ----
+// Local step ind of launch sample s: locates the cell(s), reads or draws the noise, interpolates the arrays A by
+// p.method into al[], forms f[k] = fval(al[k], coef) and advances the position in two roundings: x + v dt, + sq nz.
+// 2-D: alp arrays 0, 1 drive x (a1x for f >= 0, a2x for f < 0), 2, 3 drive y; egno 3 stores 0, 1 only (set_fns.py:98).
+template <typename R, int EGNO, int NA>
+__device__ __forceinline__ void traj_step_2d(const TrajP<R>& p, const R* const __restrict__ (&A)[NA], int ind,
+                                             unsigned long long s, double& x, double& y, double (&al)[NA],
+                                             double (&f)[NA]) {
+#pragma clang fp contract(off)
+  const size_t row = (size_t)(p.T - 1 - ind) * ((size_t)p.nx * (size_t)p.ny);
+  const int step = p.step0 + ind;
+  const TrajCell cx = traj_locate(x, p.xs, p.nx, p.Px, p.inv_dx, p.bcx, p.center_x);
+  const TrajCell cy = traj_locate(y, p.ys, p.ny, p.Py, p.inv_dy, 0, p.center_y);
+  double nz0 = 0.0, nz1 = 0.0;
+  if (p.noise_mode == 1) {
+    const size_t o = ((size_t)step * p.n + s) * 2;
+    nz0 = p.noise[o];
+    nz1 = p.noise[o + 1];
+  }
+  if (p.method == 1) {   // nearest node per axis, ties to the lower node
+    const size_t o = row + (size_t)(cx.u > 0.5 ? cx.j1 : cx.j0) * p.ny + (size_t)(cy.u > 0.5 ? cy.j1 : cy.j0);
+    R v[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) v[a] = A[a][o];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) al[a] = (double)v[a];
+  } else {               // bilinear: every corner of every array is loaded before the first use
+    const size_t o00 = row + (size_t)cx.j0 * p.ny + cy.j0, o10 = row + (size_t)cx.j1 * p.ny + cy.j0;
+    const size_t o01 = row + (size_t)cx.j0 * p.ny + cy.j1, o11 = row + (size_t)cx.j1 * p.ny + cy.j1;
+    R v[NA][4];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) {
+      v[a][0] = A[a][o00];
+      v[a][1] = A[a][o10];
+      v[a][2] = A[a][o01];
+      v[a][3] = A[a][o11];
+    }
+#pragma unroll
+    for (int a = 0; a < NA; ++a) al[a] = traj_bilinear(cx, cy, v[a]);
+  }
+  if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, step, 0, nz0, nz1);
+  // f sees x mod P on a periodic axis and the raw coordinate on a Neumann axis (run_example.py:139-145)
+  const double xf = p.bcx == 0 ? traj_pmod(x, p.Px) : x;
+  double ax = 0.0, ay = 0.0;   // egno 3: f = (alp, x) takes no coefficient, and y drifts with x
+  if constexpr (EGNO != 3) ax = traj_coef(xf), ay = traj_coef(traj_pmod(y, p.Py));
+#pragma unroll
+  for (int a = 0; a < NA; ++a) f[a] = fval<double, EGNO>(al[a], a < 2 ? ax : ay);
+  const double vx = fpos(f[0]) + fneg(f[1]);
+  const double vy = EGNO == 3 ? fpos(xf) + fneg(xf) : fpos(f[NA - 2]) + fneg(f[NA - 1]);
+  x = x + vx * p.dt;
+  y = y + vy * p.dt;
+  if (p.noise_mode) {
+    x = x + p.sq * nz0;
+    y = y + p.sq * nz1;
+  }
+}
+
+// 1-D (compute_traj_1d, run_example.py:18-52).  The grid is the reference's: ascending in [0, P).
+//   linear : traj_cell_1d;
+//   nearest: argmin |x_arr - x mod P|, first index on ties, with no wrap: past the last node's midpoint to the
+//            period's end it stays the last node.
+template <typename R, int EGNO>
+__device__ __forceinline__ void traj_step_1d(const TrajP<R>& p, const R* __restrict__ A0, const R* __restrict__ A1,
+                                             int ind, unsigned long long s, double& x, double (&al)[2],
+                                             double (&f)[2]) {
+#pragma clang fp contract(off)
+  const int n = p.nx;
+  const double* __restrict__ g = p.xs;
+  const size_t row = (size_t)(p.T - 1 - ind) * (size_t)n;
+  const int step = p.step0 + ind;
+  const double xm = traj_pmod(x, p.Px);
+  double nz = 0.0, nz_unused;
+  if (p.noise_mode == 1) nz = p.noise[(size_t)step * p.n + s];
+  if (p.method == 1) {
+    int j = (int)fmin(fmax((xm - g[0]) * p.inv_dx, 0.0), (double)(n - 1));
+    while (j > 0 && fabs(g[j - 1] - xm) <= fabs(g[j] - xm)) --j;      // ties: the first index
+    while (j < n - 1 && fabs(g[j + 1] - xm) < fabs(g[j] - xm)) ++j;
+    const R v1 = A0[row + j], v2 = A1[row + j];
+    al[0] = (double)v1;
+    al[1] = (double)v2;
+  } else {
+    const TrajCell c = traj_cell_1d(xm, g, n, p.Px, p.inv_dx);
+    const R v10 = A0[row + c.j0], v11 = A0[row + c.j1], v20 = A1[row + c.j0], v21 = A1[row + c.j1];
+    al[0] = (double)v10 + c.u * ((double)v11 - (double)v10);
+    al[1] = (double)v20 + c.u * ((double)v21 - (double)v20);
+  }
+  if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, step, 0, nz, nz_unused);
+  const double a = traj_coef(xm);
+  f[0] = fval<double, EGNO>(al[0], a);
+  f[1] = fval<double, EGNO>(al[1], a);
+  const double vel = fpos(f[0]) + fneg(f[1]);
+  x = x + vel * p.dt;
+  if (p.noise_mode) x = x + p.sq * nz;
+}
+
+// The rollout: start, the step loop and the records, [step][sample][...] so that a wave's stores are contiguous.
 template <typename R, int EGNO>
 __global__ void __launch_bounds__(256) k_traj_2d(TrajP<R> p) {
 #pragma clang fp contract(off)
@@ -145,70 +274,19 @@ __global__ void __launch_bounds__(256) k_traj_2d(TrajP<R> p) {
   const R* __restrict__ A[NA];
 #pragma unroll
   for (int a = 0; a < NA; ++a) A[a] = cur ? p.alp[1][a] : p.alp[0][a];   // no dynamic index into the argument block
-  const size_t npl = (size_t)p.nx * (size_t)p.ny;
   double x = p.x_in[2 * s], y = p.x_in[2 * s + 1];
   if (p.rec_x && p.step0 == 0) {
     p.rec_x[2 * s] = x;
     p.rec_x[2 * s + 1] = y;
   }
   for (int ind = 0; ind < p.T; ++ind) {
-    const size_t row = (size_t)(p.T - 1 - ind) * npl;
     const int step = p.step0 + ind;
-    const TrajCell cx = traj_locate(x, p.xs, p.nx, p.Px, p.inv_dx, p.bcx, p.center_x);
-    const TrajCell cy = traj_locate(y, p.ys, p.ny, p.Py, p.inv_dy, 0, p.center_y);
-    double nz0 = 0.0, nz1 = 0.0;
-    if (p.noise_mode == 1) {
-      const size_t o = ((size_t)step * p.n + s) * 2;
-      nz0 = p.noise[o];
-      nz1 = p.noise[o + 1];
-    }
-    double al[NA];
-    if (p.method == 1) {   // nearest node per axis, ties to the lower node
-      const size_t o = row + (size_t)(cx.u > 0.5 ? cx.j1 : cx.j0) * p.ny + (size_t)(cy.u > 0.5 ? cy.j1 : cy.j0);
-      R v[NA];
-#pragma unroll
-      for (int a = 0; a < NA; ++a) v[a] = A[a][o];
-#pragma unroll
-      for (int a = 0; a < NA; ++a) al[a] = (double)v[a];
-    } else {               // bilinear: every corner of every array is loaded before the first use
-      const size_t o00 = row + (size_t)cx.j0 * p.ny + cy.j0, o10 = row + (size_t)cx.j1 * p.ny + cy.j0;
-      const size_t o01 = row + (size_t)cx.j0 * p.ny + cy.j1, o11 = row + (size_t)cx.j1 * p.ny + cy.j1;
-      R v[NA][4];
-#pragma unroll
-      for (int a = 0; a < NA; ++a) {
-        v[a][0] = A[a][o00];
-        v[a][1] = A[a][o10];
-        v[a][2] = A[a][o01];
-        v[a][3] = A[a][o11];
-      }
-      const double u = cx.u, w = cy.u;
-      const double w00 = (1.0 - u) * (1.0 - w), w10 = u * (1.0 - w), w01 = (1.0 - u) * w, w11 = u * w;
-#pragma unroll
-      for (int a = 0; a < NA; ++a)
-        al[a] = w00 * (double)v[a][0] + w10 * (double)v[a][1] + w01 * (double)v[a][2] + w11 * (double)v[a][3];
-    }
-    if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, step, 0, nz0, nz1);
+    double al[NA], f[NA];
+    traj_step_2d<R, EGNO>(p, A, ind, s, x, y, al, f);
     if (p.rec_a) {
       double* ra = p.rec_a + ((size_t)step * p.n + s) * NC;
       ra[0] = al[0] + al[1];
       if constexpr (NC == 2) ra[1] = al[2] + al[3];
-    }
-    // f sees x mod P on a periodic axis and the raw coordinate on a Neumann axis (run_example.py:139-145)
-    const double xf = p.bcx == 0 ? traj_pmod(x, p.Px) : x;
-    double vx, vy;
-    if constexpr (EGNO == 3) {
-      vx = fpos(fval<double, 3>(al[0], 0.0)) + fneg(fval<double, 3>(al[1], 0.0));
-      vy = fpos(xf) + fneg(xf);
-    } else {
-      const double ax = traj_coef(xf), ay = traj_coef(traj_pmod(y, p.Py));
-      vx = fpos(fval<double, EGNO>(al[0], ax)) + fneg(fval<double, EGNO>(al[1], ax));
-      vy = fpos(fval<double, EGNO>(al[2], ay)) + fneg(fval<double, EGNO>(al[3], ay));
-    }
-    x = x + vx * p.dt;
-    y = y + vy * p.dt;
-    if (p.noise_mode) {
-      x = x + p.sq * nz0;
-      y = y + p.sq * nz1;
     }
     if (p.rec_x) {
       double* rx = p.rec_x + ((size_t)(step + 1) * p.n + s) * 2;
@@ -220,62 +298,21 @@ __global__ void __launch_bounds__(256) k_traj_2d(TrajP<R> p) {
   p.x_out[2 * s + 1] = y;
 }
 
-// 1-D (compute_traj_1d, run_example.py:18-52).  The grid is the reference's: ascending in [0, P).
-//   linear : jnp.interp(x, x_arr, alp, period=P) -- the cell before node 0 and after node nx-1 closes the period;
-//   nearest: argmin |x_arr - x mod P|, first index on ties, with no wrap: past the last node's midpoint to the
-//            period's end it stays the last node.
 template <typename R, int EGNO>
 __global__ void __launch_bounds__(256) k_traj_1d(TrajP<R> p) {
 #pragma clang fp contract(off)
   const unsigned long long s = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= p.n) return;
-  const int cur = p.ctrl->cur, n = p.nx;
+  const int cur = p.ctrl->cur;
   const R* __restrict__ A0 = cur ? p.alp[1][0] : p.alp[0][0];
   const R* __restrict__ A1 = cur ? p.alp[1][1] : p.alp[0][1];
-  const double* __restrict__ g = p.xs;
   double x = p.x_in[s];
   if (p.rec_x && p.step0 == 0) p.rec_x[s] = x;
   for (int ind = 0; ind < p.T; ++ind) {
-    const size_t row = (size_t)(p.T - 1 - ind) * (size_t)n;
     const int step = p.step0 + ind;
-    const double xm = traj_pmod(x, p.Px);
-    double nz = 0.0, nz_unused;
-    if (p.noise_mode == 1) nz = p.noise[(size_t)step * p.n + s];
-    int j = (int)fmin(fmax((xm - g[0]) * p.inv_dx, 0.0), (double)(n - 1));
-    double a1, a2;
-    if (p.method == 1) {
-      while (j > 0 && fabs(g[j - 1] - xm) <= fabs(g[j] - xm)) --j;      // ties: the first index
-      while (j < n - 1 && fabs(g[j + 1] - xm) < fabs(g[j] - xm)) ++j;
-      const R v1 = A0[row + j], v2 = A1[row + j];
-      a1 = (double)v1;
-      a2 = (double)v2;
-    } else {
-      while (j > 0 && xm < g[j]) --j;
-      while (j < n - 1 && xm > g[j + 1]) ++j;
-      int j0 = j, j1 = j + 1;
-      double lo = g[j], hi;
-      if (xm < g[0]) {          // before node 0: from the last node of the previous period
-        j0 = n - 1;
-        j1 = 0;
-        lo = g[n - 1] - p.Px;
-        hi = g[0];
-      } else if (j1 < n) {
-        hi = g[j1];
-      } else {                  // after the last node: to node 0 of the next period
-        j1 = 0;
-        hi = g[0] + p.Px;
-      }
-      const R v10 = A0[row + j0], v11 = A0[row + j1], v20 = A1[row + j0], v21 = A1[row + j1];
-      const double w = hi > lo ? (xm - lo) / (hi - lo) : 0.0;
-      a1 = (double)v10 + w * ((double)v11 - (double)v10);
-      a2 = (double)v20 + w * ((double)v21 - (double)v20);
-    }
-    if (p.noise_mode == 2) traj_normals(p.seed, p.s0 + s, step, 0, nz, nz_unused);
-    if (p.rec_a) p.rec_a[(size_t)step * p.n + s] = a1 + a2;
-    const double a = traj_coef(xm);
-    const double vel = fpos(fval<double, EGNO>(a1, a)) + fneg(fval<double, EGNO>(a2, a));
-    x = x + vel * p.dt;
-    if (p.noise_mode) x = x + p.sq * nz;
+    double al[2], f[2];
+    traj_step_1d<R, EGNO>(p, A0, A1, ind, s, x, al, f);
+    if (p.rec_a) p.rec_a[(size_t)step * p.n + s] = al[0] + al[1];
     if (p.rec_x) p.rec_x[(size_t)(step + 1) * p.n + s] = x;
   }
   p.x_out[s] = x;
