@@ -108,8 +108,23 @@ inline pdhg_policy_report policy_from_sums(const double* h, long long n_sample) 
   return r;
 }
 
+// pdhg_stats from the loop control block (rho's range is not tracked on the device)
+inline void stats_from_ctrl(const Ctrl& h, pdhg_stats* st) {
+  st->iters_run = h.iters;
+  st->status = h.done;
+  st->inner_last = h.inner_count;
+  st->inner_total = h.inner_total;
+  st->err1 = h.err1;
+  st->err2 = h.err2;
+  st->err_inner = h.err_inner;
+  st->rho_min = NAN;
+  st->rho_max = NAN;
+  st->nan_seen = h.nan_seen;
+  st->first_nan_iter = h.first_nan;
+}
+
 struct ImplBase {
-  int device = 0;   // every entry point selects it before touching the context (dispatch)
+  int device = 0;  // every entry point selects it before touching the context (dispatch)
   virtual ~ImplBase() {}
 };
 
@@ -1251,19 +1266,7 @@ struct Impl : ImplBase {
       if ((rc = read_ctrl(h))) return rc;
     }
     spec = false;
-    if (st) {
-      st->iters_run = h.iters;
-      st->status = h.done;
-      st->inner_last = h.inner_count;
-      st->inner_total = h.inner_total;
-      st->err1 = h.err1;
-      st->err2 = h.err2;
-      st->err_inner = h.err_inner;
-      st->rho_min = NAN;
-      st->rho_max = NAN;
-      st->nan_seen = h.nan_seen;
-      st->first_nan_iter = h.first_nan;
-    }
+    if (st) stats_from_ctrl(h, st);
     primal_done = false;
     return PDHG_OK;
   }
@@ -1520,17 +1523,7 @@ struct Impl : ImplBase {
     Ctrl h;
     int rc;
     if ((rc = read_ctrl(h))) return rc;
-    st->iters_run = h.iters;
-    st->status = h.done;
-    st->inner_last = h.inner_count;
-    st->inner_total = h.inner_total;
-    st->err1 = h.err1;
-    st->err2 = h.err2;
-    st->err_inner = h.err_inner;
-    st->rho_min = NAN;
-    st->rho_max = NAN;
-    st->nan_seen = h.nan_seen;
-    st->first_nan_iter = h.first_nan;
+    stats_from_ctrl(h, st);
     return PDHG_OK;
   }
 
@@ -1560,32 +1553,15 @@ struct Impl : ImplBase {
     int cur = 0;
     HIP_TRY(hipMemcpyAsync(&cur, &kp.ctrl->cur, sizeof(int), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    const size_t nphi = (size_t)(T + 1) * npl;
-    std::unique_ptr<R[]> buf(new R[nphi]);   // not value-initialised: filled before every copy out of it
-    // fp64 planes straight from the caller's arrays (same layout); fp32 through a narrowing copy
-    auto src_of = [&](const double* p, size_t cnt) -> const R* {
-      if constexpr (sizeof(R) == 8) {
-        (void)cnt;
-        return p;
-      } else {
-        for (size_t i = 0; i < cnt; ++i) buf[i] = (R)p[i];
-        return buf.get();
-      }
-    };
-    if (phi) {
-      if constexpr (kMixed) {   // phi as given: full doubles
-        H2D(px.phi, phi, nphi * sizeof(P));
-        H2D(px.phibar, phi, nphi * sizeof(P));
-        compute_row0_sq(std::vector<P>(phi, phi + npl));
-      } else {
-        const R* src = src_of(phi, nphi);
-        H2D(kp.phi, src, nphi * sizeof(R));
-        H2D(kp.phibar, src, nphi * sizeof(R));
-        compute_row0_sq(std::vector<R>(src, src + npl));
-      }
+    const size_t nphi = (size_t)(T + 1) * npl, n = (size_t)T * npl;
+    const auto buf = plane_scratch<R>(nphi, alp != nullptr);
+    if (phi) {   // narrowed once for both copies (mixed: phi as given, full doubles)
+      const P* src = as_elems<P>(phi, nphi, buf.get());
+      H2D(phi_dev(), src, nphi * sizeof(P));
+      H2D(phibar_dev(), src, nphi * sizeof(P));
+      compute_row0_sq(std::vector<P>(src, src + npl));
     }
-    const size_t n = (size_t)T * npl;
-    if (rho) H2D(kp.rho[cur], src_of(rho, n), n * sizeof(R));
+    if (rho) H2D(kp.rho[cur], as_elems<R>(rho, n, buf.get()), n * sizeof(R));
     if (alp) {
       const int nc = n_ctrl(), nar = n_alp_ref();
       for (int a = 0; a < nar; ++a)
@@ -1599,7 +1575,7 @@ struct Impl : ImplBase {
       for (int a = 0; a < nar; ++a)
         for (int c = 0; c < nc; ++c) {
           if (!live(a, c, nc)) continue;
-          for (size_t i = 0; i < n; ++i) buf[i] = (R)alp[((size_t)a * n + i) * nc + c];
+          alp_gather(buf.get(), alp, n, nc, a, c);
           H2D(kp.alp[cur][a], buf.get(), n * sizeof(R));
         }
     }
@@ -1613,100 +1589,36 @@ struct Impl : ImplBase {
 
   int set_phi_bar(const double* pbar) {
     const size_t n = (size_t)(pb.T + 1) * plane();
-    if constexpr (sizeof(P) == 8) {
-      H2D(phibar_dev(), pbar, n * sizeof(P));
-      return PDHG_OK;
-    }
-    std::vector<R> buf(n);
-    for (size_t i = 0; i < n; ++i) buf[i] = (R)pbar[i];
-    H2D(kp.phibar, buf.data(), n * sizeof(R));
+    const auto buf = plane_scratch<P>(n);
+    H2D(phibar_dev(), as_elems<P>(pbar, n, buf.get()), n * sizeof(P));
     return PDHG_OK;
   }
 
   int get_phi_bar(double* pbar) {
     HIP_TRY(hipStreamSynchronize(stream));
     const size_t n = (size_t)(pb.T + 1) * plane();
-    if constexpr (kMixed) {
-      HIP_TRY(hipMemcpy(pbar, px.phibar, n * sizeof(P), hipMemcpyDeviceToHost));
-      return PDHG_OK;
-    }
-    std::vector<R> buf(n);
-    HIP_TRY(hipMemcpy(buf.data(), kp.phibar, n * sizeof(R), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; ++i) pbar[i] = (double)buf[i];
-    return PDHG_OK;
+    return get_plane(pbar, (const P*)phibar_dev(), 0, n, plane_scratch<P>(n).get());
   }
 
   int get_work(double* out, size_t count) {
     HIP_TRY(hipStreamSynchronize(stream));
     const size_t nwork = pb.ndim == 2 ? (size_t)pb.T * kp.nb * pb.nx * kp.B : (size_t)pb.T * pb.nx;
     if (count > nwork) return fail(PDHG_ERR_ARG, "work buffer holds %zu elements", nwork);
-    std::vector<R> buf(count);
-    HIP_TRY(hipMemcpy(buf.data(), kp.work, count * sizeof(R), hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < count; ++i) out[i] = (double)buf[i];
-    return PDHG_OK;
+    return get_plane(out, (const R*)kp.work, 0, count, plane_scratch<R>(count).get());
   }
 
-  int get_state(double* phi, double* rho, double* alp) {
+  // rows [row0, row0 + rows_phi) of phi / phi_bar and [row0, row0 + rows) of rho / alp into the reference layouts
+  // (alp [nar][rows][nx][ny][nc], its dead components zero), from the current buffer set
+  int rows_out(int row0, int rows_phi, int rows, double* phi, double* pbar, double* rho, double* alp) {
     HIP_TRY(hipStreamSynchronize(stream));
     Ctrl h;
     int rc;
     if ((rc = read_ctrl(h))) return rc;
-    const int cur = h.cur;
-    const size_t npl = plane();
-    const int T = pb.T;
-    const size_t nphi = (size_t)(T + 1) * npl;
-    std::unique_ptr<R[]> buf(new R[nphi]);   // not value-initialised: every element read is copied in first
-    const size_t n = (size_t)T * npl;
-    // fp64 planes straight into the caller's arrays (same layout); fp32 through the buffer and a widening copy
-    auto plane_out = [&](double* dst, const auto* src, size_t cnt) -> int {
-      using E = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
-      if constexpr (sizeof(E) == 8) {
-        HIP_TRY(hipMemcpy(dst, src, cnt * sizeof(E), hipMemcpyDeviceToHost));
-      } else {
-        HIP_TRY(hipMemcpy(buf.get(), src, cnt * sizeof(E), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < cnt; ++i) dst[i] = (double)buf[i];
-      }
-      return PDHG_OK;
-    };
-    if (phi && (rc = plane_out(phi, (const P*)phi_dev(), nphi))) return rc;
-    if (rho && (rc = plane_out(rho, (const R*)kp.rho[cur], n))) return rc;
-    if (alp) {
-      const int nc = n_ctrl(), nar = n_alp_ref();
-      std::memset(alp, 0, sizeof(double) * n * nc * nar);
-      for (int a = 0; a < nar; ++a)
-        for (int c = 0; c < nc; ++c) {
-          if (!live(a, c, nc)) continue;
-          HIP_TRY(hipMemcpy(buf.get(), kp.alp[cur][a], n * sizeof(R), hipMemcpyDeviceToHost));
-          for (size_t i = 0; i < n; ++i) alp[((size_t)a * n + i) * nc + c] = (double)buf[i];
-        }
-    }
-    return PDHG_OK;
-  }
-
-  // rows [row0, row0 + nrows) of phi / phi_bar ([T+1]) and rho / alp ([T]) in the reference layouts
-  int get_rows(int row0, int nrows, double* phi, double* pbar, double* rho, double* alp) {
-    const int T = pb.T;
-    if (row0 < 0 || nrows < 1 || row0 + nrows > T + 1 || ((rho || alp) && row0 + nrows > T))
-      return fail(PDHG_ERR_ARG, "rows [%d, %d) outside phi [0, %d) / rho, alp [0, %d)", row0, row0 + nrows, T + 1, T);
-    HIP_TRY(hipStreamSynchronize(stream));
-    Ctrl h;
-    int rc;
-    if ((rc = read_ctrl(h))) return rc;
-    const size_t npl = plane(), n = (size_t)nrows * npl, off = (size_t)row0 * npl;
-    std::unique_ptr<R[]> buf(sizeof(R) == 8 && !alp ? nullptr : new R[n]);
-    auto rows_out = [&](double* dst, const auto* src) -> int {
-      using E = std::remove_cv_t<std::remove_pointer_t<decltype(src)>>;
-      if constexpr (sizeof(E) == 8) {
-        HIP_TRY(hipMemcpy(dst, src + off, n * sizeof(E), hipMemcpyDeviceToHost));
-      } else {
-        HIP_TRY(hipMemcpy(buf.get(), src + off, n * sizeof(E), hipMemcpyDeviceToHost));
-        for (size_t i = 0; i < n; ++i) dst[i] = (double)buf[i];
-      }
-      return PDHG_OK;
-    };
-    if (phi && (rc = rows_out(phi, (const P*)phi_dev()))) return rc;
-    if (pbar && (rc = rows_out(pbar, (const P*)phibar_dev()))) return rc;
-    if (rho && (rc = rows_out(rho, (const R*)kp.rho[h.cur]))) return rc;
+    const size_t npl = plane(), nphi = (size_t)rows_phi * npl, n = (size_t)rows * npl, off = (size_t)row0 * npl;
+    const auto buf = plane_scratch<R>(std::max(nphi, n), alp != nullptr);
+    if (phi && (rc = get_plane(phi, (const P*)phi_dev(), off, nphi, buf.get()))) return rc;
+    if (pbar && (rc = get_plane(pbar, (const P*)phibar_dev(), off, nphi, buf.get()))) return rc;
+    if (rho && (rc = get_plane(rho, (const R*)kp.rho[h.cur], off, n, buf.get()))) return rc;
     if (alp) {
       const int nc = n_ctrl(), nar = n_alp_ref();
       std::memset(alp, 0, sizeof(double) * n * nc * nar);
@@ -1714,49 +1626,23 @@ struct Impl : ImplBase {
         for (int c = 0; c < nc; ++c) {
           if (!live(a, c, nc)) continue;
           HIP_TRY(hipMemcpy(buf.get(), kp.alp[h.cur][a] + off, n * sizeof(R), hipMemcpyDeviceToHost));
-          for (size_t i = 0; i < n; ++i) alp[((size_t)a * n + i) * nc + c] = (double)buf[i];
+          alp_scatter(alp, buf.get(), n, nc, a, c);
         }
     }
     return PDHG_OK;
   }
+  // the whole window: phi [T+1], rho / alp [T]
+  int get_state(double* phi, double* rho, double* alp) { return rows_out(0, pb.T + 1, pb.T, phi, nullptr, rho, alp); }
+  // rows [row0, row0 + nrows) of phi / phi_bar ([T+1]) and rho / alp ([T])
+  int get_rows(int row0, int nrows, double* phi, double* pbar, double* rho, double* alp) {
+    const int T = pb.T;
+    if (row0 < 0 || nrows < 1 || row0 + nrows > T + 1 || ((rho || alp) && row0 + nrows > T))
+      return fail(PDHG_ERR_ARG, "rows [%d, %d) outside phi [0, %d) / rho, alp [0, %d)", row0, row0 + nrows, T + 1, T);
+    return rows_out(row0, nrows, nrows, phi, pbar, rho, alp);
+  }
 
   // ---------------- closed-loop trajectories (kernels_traj.hpp; include/pdhg.h pdhg_trajectories) ----------------
-  // Samples are staged in chunks of whole workgroups out of one allocation: the device temporaries (positions in /
-  // out, the chunk's noise, records or per-sample outputs) stay within kTrajBudget however many samples and rows the
-  // call has.  `lead` doubles come first (the policy check's partial table), then a chunk's buffers, carved by take().
-  static constexpr size_t kTrajBudget = (size_t)64 << 20;
-  struct SampleChunks {
-    size_t n;                 // samples of the call
-    hipStream_t stream;
-    size_t m = 0;             // samples per chunk: a multiple of 256, or n
-    double* base = nullptr;   // freed on every way out
-    double* next = nullptr;
-    ~SampleChunks() { if (base) hipFree(base); }
-    // per: bytes a sample takes in the chunk buffers; 0 (grid starts with the report only): the call is one chunk
-    int alloc(size_t per, size_t lead, const char* what) {
-      m = std::min(n, per ? std::max<size_t>(kTrajBudget / per, 256) / 256 * 256 : n);
-      const size_t bytes = lead * sizeof(double) + m * per;
-      if (hipMalloc((void**)&base, bytes) != hipSuccess)
-        return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the %s failed", bytes, what);
-      next = base + lead;
-      return PDHG_OK;
-    }
-    double* take(bool on, size_t doubles) { return on ? std::exchange(next, next + doubles) : nullptr; }
-    // rows [j][c0 .. c0 + mc) of a host array [rows][n][w] into the dense device array [rows][mc][w], and back; an
-    // array that is not there (null on either side) moves nothing.  d is take()'s, const only in the argument block.
-    int up(const double* d, const double* h, int rows, size_t c0, size_t mc, size_t w) const {
-      for (int j = 0; d && h && j < rows; ++j)
-        HIP_TRY(hipMemcpyAsync(const_cast<double*>(d) + (size_t)j * mc * w, h + ((size_t)j * n + c0) * w,
-                               mc * w * sizeof(double), hipMemcpyHostToDevice, stream));
-      return PDHG_OK;
-    }
-    int down(double* h, const double* d, int rows, size_t c0, size_t mc, size_t w) const {
-      for (int j = 0; d && h && j < rows; ++j)
-        HIP_TRY(hipMemcpyAsync(h + ((size_t)j * n + c0) * w, d + (size_t)j * mc * w, mc * w * sizeof(double),
-                               hipMemcpyDeviceToHost, stream));
-      return PDHG_OK;
-    }
-  };
+  // Samples are staged in chunks (staging.hpp SampleChunks; the rollout's chunk: RolloutLayout).
   std::vector<double> grid_x, grid_y;   // the grid coordinates in fp64 (kp.ax / kp.ay hold f coefficients in R)
   double* d_xs64 = nullptr;             // ... on the device, uploaded by the first call
   double* d_ys64 = nullptr;
@@ -1842,25 +1728,25 @@ struct Impl : ImplBase {
     if ((rc = traj_ready(o))) return rc;
     const bool noisy = pb.epsl > 0;
     const size_t n = (size_t)o.n_sample;
-    const size_t w_x = (size_t)nd, w_a = (size_t)nc;   // doubles per sample and row
-    const size_t per = sizeof(double) * (2 * w_x + (noisy && noise ? (size_t)T * w_x : 0) +
-                                         (traj_x ? (size_t)(T + 1) * w_x : 0) + (traj_alp ? (size_t)T * w_a : 0));
-    SampleChunks st{n, stream};
-    if ((rc = st.alloc(per, 0, "trajectory chunk"))) return rc;
+    const RolloutLayout lay{T, (size_t)nd, (size_t)nc, noisy && noise, traj_x != nullptr, traj_alp != nullptr};
+    const size_t w_x = lay.w_x, w_a = lay.w_a;
+    SampleChunks st(n, stream);
+    if ((rc = st.alloc(lay.per(), 0, "trajectory chunk"))) return rc;
+    const RolloutLayout::Ptrs d = lay.carve(st);
     TrajP<R> a = traj_params(o, noisy ? (noise ? 1 : 2) : 0);
-    a.x_in = st.take(true, st.m * w_x);
-    a.x_out = st.take(true, st.m * w_x);
-    a.noise = st.take(noisy && noise, (size_t)T * st.m * w_x);
-    a.rec_x = st.take(traj_x != nullptr, (size_t)(T + 1) * st.m * w_x);
-    a.rec_a = st.take(traj_alp != nullptr, (size_t)T * st.m * w_a);
+    a.x_in = d.x_in;
+    a.x_out = d.x_out;
+    a.noise = d.noise;
+    a.rec_x = d.rec_x;
+    a.rec_a = d.rec_a;
     for (size_t c0 = 0; c0 < n; c0 += st.m) {
       const size_t mc = std::min(st.m, n - c0);
-      if ((rc = st.up(a.x_in, x_init, 1, c0, mc, w_x)) || (rc = st.up(a.noise, noise, T, c0, mc, w_x))) return rc;
+      if ((rc = st.up(d.x_in, x_init, 0, 1, c0, mc, w_x)) || (rc = st.up(d.noise, noise, 0, T, c0, mc, w_x))) return rc;
       a.n = mc;
       a.s0 = (unsigned long long)o.sample_offset + c0;
       if ((rc = launch_traj(a))) return rc;
-      if ((rc = st.down(x_final, a.x_out, 1, c0, mc, w_x)) || (rc = st.down(traj_x, a.rec_x, T + 1, c0, mc, w_x)) ||
-          (rc = st.down(traj_alp, a.rec_a, T, c0, mc, w_a)))
+      if ((rc = st.down(x_final, d.x_out, 0, 1, c0, mc, w_x)) || (rc = st.down(traj_x, d.rec_x, 0, T + 1, c0, mc, w_x)) ||
+          (rc = st.down(traj_alp, d.rec_a, 0, T, c0, mc, w_a)))
         return rc;
       HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
     }
@@ -1903,7 +1789,7 @@ struct Impl : ImplBase {
     const size_t per = sizeof(double) * ((x_init ? w_x : 0) + (x_final ? w_x : 0) +
                                          (noisy && noise ? (size_t)T * w_x : 0) + (running ? 1 : 0) +
                                          (terminal ? 1 : 0) + (value ? 1 : 0));
-    SampleChunks st{n, stream};
+    SampleChunks st(n, stream);
     if ((rc = st.alloc(per, (nwg + 1) * kNumSums, "policy check"))) return rc;
     PolP<R, P> a{};
     a.t = traj_params(o, noisy ? (noise ? 1 : 2) : 0);
@@ -1922,13 +1808,13 @@ struct Impl : ImplBase {
     a.partials = st.base;
     for (size_t c0 = 0; c0 < n; c0 += st.m) {
       const size_t mc = std::min(st.m, n - c0);
-      if ((rc = st.up(a.t.x_in, x_init, 1, c0, mc, w_x)) || (rc = st.up(a.t.noise, noise, T, c0, mc, w_x))) return rc;
+      if ((rc = st.up(a.t.x_in, x_init, 0, 1, c0, mc, w_x)) || (rc = st.up(a.t.noise, noise, 0, T, c0, mc, w_x))) return rc;
       a.t.n = mc;
       a.t.s0 = (unsigned long long)o.sample_offset + c0;
       a.g0 = c0;
       if ((rc = launch_policy(a))) return rc;
-      if ((rc = st.down(x_final, a.t.x_out, 1, c0, mc, w_x)) || (rc = st.down(running, a.running, 1, c0, mc, 1)) ||
-          (rc = st.down(terminal, a.term, 1, c0, mc, 1)) || (rc = st.down(value, a.value, 1, c0, mc, 1)))
+      if ((rc = st.down(x_final, a.t.x_out, 0, 1, c0, mc, w_x)) || (rc = st.down(running, a.running, 0, 1, c0, mc, 1)) ||
+          (rc = st.down(terminal, a.term, 0, 1, c0, mc, 1)) || (rc = st.down(value, a.value, 0, 1, c0, mc, 1)))
         return rc;
       HIP_TRY(hipStreamSynchronize(stream));   // the chunk buffers are reused
     }
@@ -1944,8 +1830,7 @@ struct Impl : ImplBase {
 
   // ---------------- solution report (kernels_report.hpp; include/pdhg.h pdhg_report_state / _rows) ----------------
   // Read-only on everything the iteration owns: the kernels take kp by value and write only the report's own partial
-  // table (allocated by the first call) and, for report_rows, staged field planes of at most kReportBudget bytes.
-  static constexpr size_t kReportBudget = (size_t)64 << 20;
+  // table (allocated by the first call) and, for report_rows, staged field planes of at most kReportBudget bytes (staging.hpp RowChunks).
   // y per lane of the tile kernel: 16-B loads of phi (fp64 and mixed: 2 doubles; the mixed kernel spilled 70 VGPRs
   // at 4 and ran behind the per-point kernel), fp32: 4 floats
   static constexpr int kRepYpl = sizeof(P) == 8 ? 2 : 4;
@@ -2054,37 +1939,17 @@ struct Impl : ImplBase {
   }
   int slab_report_rows(const void* phi_prev, int row0, int nrows, double* d_hj, double* d_cont) {
     int rc, rows = 0;
-    if (row0 >= pb.T || nrows > pb.T - row0)
-      return fail(PDHG_ERR_ARG, "%d rows from row %d outside the slab's residual rows [0, %d)", nrows, row0, pb.T);
-    if ((rc = slab_report_halo(phi_prev))) return rc;
+    if ((rc = rows_inside(row0, nrows, pb.T, "the slab's")) || (rc = slab_report_halo(phi_prev))) return rc;
     if (!d_hj && !d_cont) return PDHG_OK;
     return launch_report(row0, row0 + nrows, d_hj, d_cont, &rows);
   }
   int report_rows(int row0, int nrows, double* hj, double* cont) {
-    int rc, rows = 0;
-    if ((rc = report_ready())) return rc;
-    if (row0 >= pb.T || nrows > pb.T - row0)   // (no row0 + nrows: it may not fit an int)
-      return fail(PDHG_ERR_ARG, "%d rows from row %d outside the residual rows [0, %d)", nrows, row0, pb.T);
-    if (!hj && !cont) return PDHG_OK;
-    const size_t npl = plane(), per = npl * sizeof(double) * ((hj ? 1 : 0) + (cont ? 1 : 0));
-    const int m = (int)std::min<size_t>((size_t)nrows, std::max<size_t>(kReportBudget / per, 1));   // rows per chunk
-    struct Tmp {   // the chunk planes: one allocation, freed on every way out
-      double* p = nullptr;
-      ~Tmp() { if (p) hipFree(p); }
-    } tmp;
-    if (hipMalloc((void**)&tmp.p, (size_t)m * per) != hipSuccess)
-      return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the report rows failed", (size_t)m * per);
-    double* d_hj = hj ? tmp.p : nullptr;
-    double* d_cont = cont ? tmp.p + (hj ? (size_t)m * npl : 0) : nullptr;
-    for (int c0 = 0; c0 < nrows; c0 += m) {
-      const int mc = std::min(m, nrows - c0);
-      if ((rc = launch_report(row0 + c0, row0 + c0 + mc, d_hj, d_cont, &rows))) return rc;
-      const size_t nb = (size_t)mc * npl * sizeof(double);
-      if (hj) HIP_TRY(hipMemcpyAsync(hj + (size_t)c0 * npl, d_hj, nb, hipMemcpyDeviceToHost, stream));
-      if (cont) HIP_TRY(hipMemcpyAsync(cont + (size_t)c0 * npl, d_cont, nb, hipMemcpyDeviceToHost, stream));
-      HIP_TRY(hipStreamSynchronize(stream));   // the chunk planes are reused
-    }
-    return PDHG_OK;
+    int rc;
+    if ((rc = report_ready()) || (rc = rows_inside(row0, nrows, pb.T))) return rc;
+    return RowChunks{stream, plane(), hj, cont}.run(nrows, [&](int c0, int mc, double* d_hj, double* d_cont) {
+      int rows = 0;
+      return launch_report(row0 + c0, row0 + c0 + mc, d_hj, d_cont, &rows);
+    });
   }
 
   int init_state(const double* g) {
@@ -2094,18 +1959,19 @@ struct Impl : ImplBase {
     std::vector<P> row(npl);   // phi's type (mixed: g as given)
     for (size_t i = 0; i < npl; ++i) row[i] = (P)g[i];
     compute_row0_sq(row);
-    P* d_row;
-    HIP_TRY(hipMalloc((void**)&d_row, npl * sizeof(P)));
-    H2D(d_row, row.data(), npl * sizeof(P));
-    const int grid = 4096;
-    hipLaunchKernelGGL((k_bcast_rows<P>), dim3(grid), dim3(256), 0, stream, phi_dev(), d_row, npl, T + 1);
-    hipLaunchKernelGGL((k_bcast_rows<P>), dim3(grid), dim3(256), 0, stream, phibar_dev(), d_row, npl, T + 1);
-    hipLaunchKernelGGL((k_fill<R>), dim3(grid), dim3(256), 0, stream, kp.rho[0], (size_t)T * npl, (R)pb.c_on_rho);
+    DevBuf d_row;   // freed on every way out
+    HIP_TRY(d_row.alloc(npl * sizeof(P)));
+    H2D(d_row.p, row.data(), npl * sizeof(P));
+    const dim3 grid(4096), block(256);
+    const size_t n = (size_t)T * npl;
+    int rc;
+    if ((rc = launch(k_bcast_rows<P>, grid, block, 0, phi_dev(), (const P*)d_row.p, npl, T + 1)) ||
+        (rc = launch(k_bcast_rows<P>, grid, block, 0, phibar_dev(), (const P*)d_row.p, npl, T + 1)) ||
+        (rc = launch(k_fill<R>, grid, block, 0, kp.rho[0], n, (R)pb.c_on_rho)))
+      return rc;
     for (int a = 0; a < pp.na; ++a)
-      hipLaunchKernelGGL((k_fill<R>), dim3(grid), dim3(256), 0, stream, kp.alp[0][a], (size_t)T * npl, (R)0);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(stream));
-    hipFree(d_row);
+      if ((rc = launch(k_fill<R>, grid, block, 0, kp.alp[0][a], n, (R)0))) return rc;
+    HIP_TRY(hipStreamSynchronize(stream));   // d_row is read until here
     Ctrl h{};
     h.row0_sq = row0_sq;
     H2D(kp.ctrl, &h, sizeof(Ctrl));

@@ -39,6 +39,7 @@ int fail(int code, const char* fmt, ...) {
 
 }  // namespace
 
+#include "staging.hpp"
 #include "ctx_impl.hpp"
 
 namespace {
@@ -120,6 +121,21 @@ int slab_device(pdhg_ctx* ctx, int* device) {
     *device = d;
     return (int)PDHG_OK;
   });
+}
+
+// the option checks every rollout and the policy check share (ndim 2: the periods of both axes; n_may_be_zero: grid
+// starts, where n_sample 0 stands for the strided grid's count)
+int check_traj_opts(const pdhg_traj_opts& o, int ndim, bool n_may_be_zero) {
+  if (o.n_sample < (n_may_be_zero ? 0 : 1))
+    return fail(PDHG_ERR_ARG, n_may_be_zero ? "n_sample must be 0 or the strided grid's count" : "n_sample must be >= 1");
+  if (o.sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
+  if (o.method != 0 && o.method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", o.method);
+  if (!(o.x_period > 0) || (ndim == 2 && !(o.y_period > 0))) return fail(PDHG_ERR_ARG, "periods must be > 0");
+  return PDHG_OK;
+}
+// the row range of the three report-rows entry points (its upper end is checked against the context's rows)
+int check_row_range(int row0, int nrows) {
+  return row0 < 0 || nrows < 1 ? fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0, nrows) : (int)PDHG_OK;
 }
 
 // the problem checks of pdhg_create (before any device is touched) and pdhg_plan_info
@@ -344,13 +360,9 @@ int pdhg_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, const double* x
   if (ctx && reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
     return fail(PDHG_ERR_UNSUPPORTED, "trajectories need a single context (pdhg_create), not a multi-device one");
   if (!opts || !x_init) return fail(PDHG_ERR_ARG, "null opts or x_init");
-  if (opts->n_sample < 1) return fail(PDHG_ERR_ARG, "n_sample must be >= 1");
-  if (opts->sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
-  if (opts->method != 0 && opts->method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", opts->method);
   return dispatch(ctx, [&](auto& im) {
-    if (!(opts->x_period > 0) || (im.pb.ndim == 2 && !(opts->y_period > 0)))
-      return fail(PDHG_ERR_ARG, "periods must be > 0");
-    return im.trajectories(*opts, x_init, noise, x_final, traj_x, traj_alp);
+    const int rc = check_traj_opts(*opts, im.pb.ndim, false);
+    return rc ? rc : im.trajectories(*opts, x_init, noise, x_final, traj_x, traj_alp);
   });
 }
 
@@ -362,16 +374,12 @@ int pdhg_policy_eval(pdhg_ctx* ctx, const pdhg_policy_opts* opts, const double* 
   if (reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
     return fail(PDHG_ERR_UNSUPPORTED, "the policy check needs a single context (pdhg_create), not a multi-device one");
   const pdhg_traj_opts& o = opts->traj;
-  if (o.method != 0 && o.method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", o.method);
   if (opts->terminal != 0 && opts->terminal != 1)
     return fail(PDHG_ERR_ARG, "terminal %d: 0 phi row 0 at x_final or 1 none", opts->terminal);
-  if (o.sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
-  if (x_init && o.n_sample < 1) return fail(PDHG_ERR_ARG, "n_sample must be >= 1 with x_init");
-  if (!x_init && o.n_sample < 0) return fail(PDHG_ERR_ARG, "n_sample must be 0 or the strided grid's count");
   if (!report && !running && !terminal && !value && !x_final)
     return fail(PDHG_ERR_ARG, "report and every output are null: nothing to compute");
   return dispatch(ctx, [&](auto& im) {
-    if (!(o.x_period > 0) || (im.pb.ndim == 2 && !(o.y_period > 0))) return fail(PDHG_ERR_ARG, "periods must be > 0");
+    if (int rc = check_traj_opts(o, im.pb.ndim, !x_init)) return rc;
     if (!x_init && (opts->stride_x < 1 || (im.pb.ndim == 2 && opts->stride_y < 1)))
       return fail(PDHG_ERR_ARG, "grid starts need strides >= 1, not (%d, %d)", opts->stride_x, opts->stride_y);
     return im.policy_eval(*opts, x_init, noise, report, running, terminal, value, x_final);
@@ -387,7 +395,7 @@ int pdhg_report_state(pdhg_ctx* ctx, pdhg_report* out) {
 }
 int pdhg_report_rows(pdhg_ctx* ctx, int row0, int nrows, double* hj, double* cont) {
   if (!ctx) return fail(PDHG_ERR_ARG, "null context");
-  if (row0 < 0 || nrows < 1) return fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0, nrows);
+  if (int rc = check_row_range(row0, nrows)) return rc;
   if (reinterpret_cast<const CtxBox*>(ctx)->magic == kMultiMagic)
     return fail(PDHG_ERR_UNSUPPORTED, "the report needs a single context (pdhg_create), not a multi-device one");
   return dispatch(ctx, [&](auto& im) { return im.report_rows(row0, nrows, hj, cont); });
@@ -508,20 +516,20 @@ int pdhg_slab_report(pdhg_ctx* ctx, const void* phi_prev_rowT, double* sums) {
 }
 int pdhg_slab_report_rows(pdhg_ctx* ctx, const void* phi_prev_rowT, int row0_local, int nrows, double* d_hj,
                           double* d_cont) {
-  if (row0_local < 0 || nrows < 1) return fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0_local, nrows);
+  if (int rc = check_row_range(row0_local, nrows)) return rc;
   return slab_dispatch(ctx, [&](auto& im) { return im.slab_report_rows(phi_prev_rowT, row0_local, nrows, d_hj, d_cont); });
 }
 int pdhg_slab_trajectories(pdhg_ctx* ctx, const pdhg_traj_opts* opts, int step0, long long n, const double* d_x_in,
                            const double* d_noise, double* d_x_out, double* d_rec_x, double* d_rec_a) {
   if (!opts || !d_x_in || !d_x_out) return fail(PDHG_ERR_ARG, "null opts, x_in or x_out");
   if (n < 1 || step0 < 0) return fail(PDHG_ERR_ARG, "n must be >= 1 and step0 >= 0");
-  if (opts->sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
-  if (opts->method != 0 && opts->method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", opts->method);
-  if (!(opts->x_period > 0) || !(opts->y_period > 0)) return fail(PDHG_ERR_ARG, "periods must be > 0");
+  pdhg_traj_opts o = *opts;
+  o.n_sample = n;   // the samples of this launch (opts->n_sample is not read); a t-slab is always 2-D
+  if (int rc = check_traj_opts(o, 2, false)) return rc;
   return slab_dispatch(ctx, [&](auto& im) {
     if (step0 > im.slab_Tg - im.slab_j0 - im.pb.T)
       return fail(PDHG_ERR_ARG, "step0 %d: the slabs after this one hold %d rows", step0, im.slab_Tg - im.slab_j0 - im.pb.T);
-    return im.slab_trajectories(*opts, step0, (unsigned long long)n, d_x_in, d_noise, d_x_out, d_rec_x, d_rec_a);
+    return im.slab_trajectories(o, step0, (unsigned long long)n, d_x_in, d_noise, d_x_out, d_rec_x, d_rec_a);
   });
 }
 int pdhg_slab_status(pdhg_ctx* ctx, pdhg_stats* st) {

@@ -27,6 +27,7 @@
 // Included by pdhg_api.hip after the C ABI (uses the slab entry points and, for the lagged done read, the
 // slab context's control block).
 #pragma once
+#include <deque>
 #include <vector>
 
 namespace pdhg {
@@ -453,77 +454,68 @@ struct pdhg_multi {
     // the device loop control of Impl::iterate: at most two windows of 8 iterations ahead of the device,
     // the done flag of the window before the last one read without draining the pipeline
     const int window = 8;
-    std::vector<hipEvent_t> evs;
-    int ret = PDHG_OK;
-    for (int it = 0; it < n && ret == PDHG_OK; ++it) {
-      if ((ret = step(tau, sigma, eps, k))) break;
+    struct WindowEvents {   // of this call alone, on slab 0's device: waited for and destroyed on every way out
+      int device;
+      std::vector<hipEvent_t> ev;
+      ~WindowEvents() {
+        hipSetDevice(device);
+        for (auto e : ev) {
+          hipEventSynchronize(e);
+          hipEventDestroy(e);
+        }
+      }
+    } evs{dev[0], {}};
+    for (int it = 0; it < n; ++it) {
+      if ((rc = step(tau, sigma, eps, k))) return rc;
       if ((it + 1) % window == 0 && it + 1 < n) {
         hipEvent_t e;
-        if ((ret = event(0, &e))) break;
-        if ((ret = rec(e, 0, st[0]))) break;
-        evs.push_back(e);
-        if (evs.size() >= 2) {
+        if (on(0)) return fail(PDHG_ERR_HIP, "hipSetDevice(%d)", dev[0]);
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        evs.ev.push_back(e);
+        if ((rc = rec(e, 0, st[0]))) return rc;
+        if (evs.ev.size() >= 2) {
           int done = 0;
-          if (hipEventSynchronize(evs[evs.size() - 2]) != hipSuccess) { ret = fail(PDHG_ERR_HIP, "event sync"); break; }
-          if ((ret = slab_done_flag(s[0], &done))) break;
+          if (hipEventSynchronize(evs.ev[evs.ev.size() - 2]) != hipSuccess) return fail(PDHG_ERR_HIP, "event sync");
+          if ((rc = slab_done_flag(s[0], &done))) return rc;
           if (done) break;
         }
       }
     }
-    for (auto e : evs) {   // drop the window events (created through event(): remove from the pool)
-      for (size_t i = 0; i < all_events.size(); ++i)
-        if (all_events[i] == e) {
-          hipSetDevice(event_dev[i]);
-          hipEventSynchronize(e);
-          hipEventDestroy(e);
-          all_events.erase(all_events.begin() + i);
-          event_dev.erase(event_dev.begin() + i);
-          break;
-        }
-    }
-    if (ret) return ret;
     pdhg_stats h{};
     if ((rc = pdhg_slab_status(s[0], &h))) return rc;
     if (out) *out = h;
     return PDHG_OK;
   }
 
+  // slab r's rows between the window's arrays and the slab's own (to_slab: window -> slab), null arrays skipped: phi
+  // rows [from, Tr] of the slab = window rows j0 + [from, Tr], rho and every alp array rows [0, Tr) = j0 + [0, Tr)
+  void slice(int r, bool to_slab, int from, double* phi, double* rho, double* alp, double* ph, double* rh, double* al) {
+    const size_t npl = (size_t)pb.nx * pb.ny;
+    const int T = pb.T, Tr = j1[r] - j0[r];
+    auto rows = [&](double* win, size_t wrow, double* sl, size_t srow, size_t n, size_t row_elems) {
+      double *w = win + wrow * row_elems, *q = sl + srow * row_elems;
+      if (to_slab) std::copy(w, w + n * row_elems, q);
+      else std::copy(q, q + n * row_elems, w);
+    };
+    if (phi) rows(phi, j0[r] + from, ph, from, Tr + 1 - from, npl);
+    if (rho) rows(rho, j0[r], rh, 0, Tr, npl);
+    for (int a = 0; alp && a < nar; ++a) rows(alp, (size_t)a * T + j0[r], al, (size_t)a * Tr, Tr, npl * nc);
+  }
   // reference layouts, whole window: phi [T+1][nx][ny], rho [T][nx][ny], alp [nar][T][nx][ny][nc]
   int state(bool set, double* phi, double* rho, double* alp) {
     const size_t npl = (size_t)pb.nx * pb.ny;
-    const int T = pb.T;
     int rc;
     if ((rc = full_barrier())) return rc;   // the state copies are synchronous: drain the slab streams
     for (int r = 0; r < P; ++r) {
       const int Tr = j1[r] - j0[r];
       std::vector<double> ph(phi ? (size_t)(Tr + 1) * npl : 0), rh(rho ? (size_t)Tr * npl : 0),
           al(alp ? (size_t)nar * Tr * npl * nc : 0);
-      if (set) {
-        if (phi) std::copy(phi + (size_t)j0[r] * npl, phi + (size_t)(j1[r] + 1) * npl, ph.begin());
-        if (rho) std::copy(rho + (size_t)j0[r] * npl, rho + (size_t)j1[r] * npl, rh.begin());
-        if (alp)
-          for (int a = 0; a < nar; ++a)
-            std::copy(alp + ((size_t)a * T + j0[r]) * npl * nc, alp + ((size_t)a * T + j1[r]) * npl * nc,
-                      al.begin() + (size_t)a * Tr * npl * nc);
-        if ((rc = pdhg_set_state(s[r], phi ? ph.data() : nullptr, rho ? rh.data() : nullptr,
-                                 alp ? al.data() : nullptr)))
-          return rc;
-      } else {
-        if ((rc = pdhg_get_state(s[r], phi ? ph.data() : nullptr, rho ? rh.data() : nullptr,
-                                 alp ? al.data() : nullptr)))
-          return rc;
-        // phi rows j0..j1 of slab r; row j0 is slab r-1's last row too (the same values: row 0 of a slab is
-        // refreshed from the previous slab only through phi_bar, so take each slab's own rows 1..Tr)
-        if (phi) {
-          const int from = (r == 0) ? 0 : 1;
-          std::copy(ph.begin() + (size_t)from * npl, ph.end(), phi + (size_t)(j0[r] + from) * npl);
-        }
-        if (rho) std::copy(rh.begin(), rh.end(), rho + (size_t)j0[r] * npl);
-        if (alp)
-          for (int a = 0; a < nar; ++a)
-            std::copy(al.begin() + (size_t)a * Tr * npl * nc, al.begin() + (size_t)(a + 1) * Tr * npl * nc,
-                      alp + ((size_t)a * T + j0[r]) * npl * nc);
-      }
+      double *p = phi ? ph.data() : nullptr, *q = rho ? rh.data() : nullptr, *c = alp ? al.data() : nullptr;
+      if (set) slice(r, true, 0, phi, rho, alp, p, q, c);
+      if ((rc = set ? pdhg_set_state(s[r], p, q, c) : pdhg_get_state(s[r], p, q, c))) return rc;
+      // phi rows j0..j1 of slab r; row j0 is slab r-1's last row too (the same values: row 0 of a slab is refreshed
+      // from the previous slab only through phi_bar, so take each slab's own rows 1..Tr)
+      if (!set) slice(r, false, r == 0 ? 0 : 1, phi, rho, alp, p, q, c);
     }
     return PDHG_OK;
   }
@@ -589,32 +581,20 @@ struct pdhg_multi {
   // global rows [row0, row0 + nrows): per slab its part of the range, staged on the slab's device in row chunks
   int report_rows(int row0, int nrows, double* hj, double* cont) {
     int rc;
-    if (row0 >= pb.T || nrows > pb.T - row0)
-      return fail(PDHG_ERR_ARG, "%d rows from row %d outside the residual rows [0, %d)", nrows, row0, pb.T);
+    if ((rc = rows_inside(row0, nrows, pb.T))) return rc;
     if (!hj && !cont) return PDHG_OK;
     if ((rc = report_halos())) return rc;
-    const size_t npl = (size_t)pb.nx * pb.ny, per = npl * sizeof(double) * ((hj ? 1 : 0) + (cont ? 1 : 0));
+    const size_t npl = (size_t)pb.nx * pb.ny;
     for (int r = 0; r < P; ++r) {
       const int a = std::max(row0, j0[r]), e = std::min(row0 + nrows, j1[r]);
       if (a >= e) continue;
-      const int m = (int)std::min<size_t>((size_t)(e - a), std::max<size_t>(kRowsBudget / per, 1));   // rows per chunk
       if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
-      struct Tmp {   // the chunk planes: one allocation, freed on every way out
-        double* p = nullptr;
-        ~Tmp() { if (p) hipFree(p); }
-      } tmp;
-      if (hipMalloc((void**)&tmp.p, (size_t)m * per) != hipSuccess)
-        return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the report rows failed", (size_t)m * per);
-      double* d_hj = hj ? tmp.p : nullptr;
-      double* d_cont = cont ? tmp.p + (hj ? (size_t)m * npl : 0) : nullptr;
-      for (int c0 = a; c0 < e; c0 += m) {
-        const int mc = std::min(m, e - c0);
-        if ((rc = pdhg_slab_report_rows(s[r], phi_prev(r), c0 - j0[r], mc, d_hj, d_cont))) return rc;
-        const size_t nb = (size_t)mc * npl * sizeof(double);
-        if (hj) HIP_TRY(hipMemcpyAsync(hj + (size_t)(c0 - row0) * npl, d_hj, nb, hipMemcpyDeviceToHost, st[r]));
-        if (cont) HIP_TRY(hipMemcpyAsync(cont + (size_t)(c0 - row0) * npl, d_cont, nb, hipMemcpyDeviceToHost, st[r]));
-        HIP_TRY(hipStreamSynchronize(st[r]));   // the chunk planes are reused
-      }
+      const size_t off = (size_t)(a - row0) * npl;   // of the slab's first row in the caller's arrays
+      const RowChunks rows{st[r], npl, hj ? hj + off : nullptr, cont ? cont + off : nullptr};
+      if ((rc = rows.run(e - a, [&](int c0, int mc, double* d_hj, double* d_cont) {
+            return pdhg_slab_report_rows(s[r], phi_prev(r), a - j0[r] + c0, mc, d_hj, d_cont);
+          })))
+        return rc;
     }
     return full_barrier();
   }
@@ -628,33 +608,24 @@ struct pdhg_multi {
     int rc;
     const int T = pb.T;
     const bool noisy = pb.epsl > 0;
-    const size_t n = (size_t)o.n_sample, w_x = 2, w_a = (size_t)nc;
-    const size_t per = sizeof(double) * (2 * w_x + (noisy && noise ? (size_t)T * w_x : 0) +
-                                         (traj_x ? (size_t)(T + 1) * w_x : 0) + (traj_alp ? (size_t)T * w_a : 0));
-    size_t m = std::max<size_t>(kSampleBudget / per, 256) / 256 * 256;   // whole workgroups per chunk
-    m = std::min(m, n);
-    struct Tmp {
-      std::vector<std::pair<int, double*>> p;   // (device, buffer)
-      ~Tmp() {
-        for (auto& q : p) {
-          hipSetDevice(q.first);
-          hipFree(q.second);
-        }
-      }
-    } tmp;
-    std::vector<double*> base(P, nullptr);
+    const size_t n = (size_t)o.n_sample;
+    const RolloutLayout lay{T, 2, (size_t)nc, noisy && noise, traj_x != nullptr, traj_alp != nullptr};
+    const size_t w_x = lay.w_x, w_a = lay.w_a;
+    std::deque<SampleChunks> bufs;            // one per distinct device, freed on every way out
+    std::vector<RolloutLayout::Ptrs> ptrs;    // ... and its buffers
+    std::vector<int> of(P, -1);               // slab -> its device's entry
     if ((rc = full_barrier())) return rc;
     for (int r = 0; r < P; ++r) {
-      for (auto& q : tmp.p)
-        if (q.first == dev[r]) base[r] = q.second;
-      if (base[r]) continue;
+      for (int q = 0; q < r && of[r] < 0; ++q)
+        if (dev[q] == dev[r]) of[r] = of[q];
+      if (of[r] >= 0) continue;
       if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
-      if (hipMalloc((void**)&base[r], m * per) != hipSuccess)
-        return fail(PDHG_ERR_NOMEM, "hipMalloc(%zu bytes) for the trajectory chunk failed", m * per);
-      tmp.p.push_back({dev[r], base[r]});
+      of[r] = (int)bufs.size();
+      bufs.emplace_back(n, st[r], dev[r]);
+      if ((rc = bufs.back().alloc(lay.per(), 0, "trajectory chunk"))) return rc;
+      ptrs.push_back(lay.carve(bufs.back()));
     }
-    const size_t o_out = m * w_x, o_noise = 2 * m * w_x, o_rx = o_noise + (noisy && noise ? (size_t)T * m * w_x : 0),
-                 o_ra = o_rx + (traj_x ? (size_t)(T + 1) * m * w_x : 0);
+    const size_t m = bufs[0].m;
     for (size_t c0 = 0; c0 < n; c0 += m) {
       const size_t mc = std::min(m, n - c0);
       pdhg_traj_opts oc = o;
@@ -662,41 +633,30 @@ struct pdhg_multi {
       oc.sample_offset = o.sample_offset + (long long)c0;
       int step0 = 0;
       for (int r = P - 1; r >= 0; --r) {
-        const int Tr = j1[r] - j0[r];
-        double* d_in = base[r];
-        double* d_out = base[r] + o_out;
-        double* d_noise = noisy && noise ? base[r] + o_noise : nullptr;
-        double* d_rx = traj_x ? base[r] + o_rx : nullptr;
-        double* d_ra = traj_alp ? base[r] + o_ra : nullptr;
+        const int Tr = j1[r] - j0[r], rx0 = step0 == 0 ? 0 : step0 + 1;   // rx0: traj_x row 0 is the first slab's
+        const RolloutLayout::Ptrs& d = ptrs[of[r]];
+        SampleChunks& sc = bufs[of[r]];
+        sc.stream = st[r];
         if (on(r)) return fail(PDHG_ERR_HIP, "hipSetDevice");
         if (r == P - 1) {
-          HIP_TRY(hipMemcpyAsync(d_in, x_init + c0 * w_x, mc * w_x * sizeof(double), hipMemcpyHostToDevice, st[r]));
+          if ((rc = sc.up(d.x_in, x_init, 0, 1, c0, mc, w_x))) return rc;
         } else if ((rc = wait(r, st[r], b[r + 1].pb)) ||
-                   (rc = copy(r, st[r], d_in, r + 1, base[r + 1] + o_out, mc * w_x * sizeof(double)))) {
+                   (rc = copy(r, st[r], d.x_in, r + 1, ptrs[of[r + 1]].x_out, mc * w_x * sizeof(double)))) {
           return rc;
         }
-        for (int j = step0; d_noise && j < step0 + Tr; ++j)
-          HIP_TRY(hipMemcpyAsync(d_noise + (size_t)j * mc * w_x, noise + ((size_t)j * n + c0) * w_x,
-                                 mc * w_x * sizeof(double), hipMemcpyHostToDevice, st[r]));
-        if ((rc = pdhg_slab_trajectories(s[r], &oc, step0, (long long)mc, d_in, d_noise, d_out, d_rx, d_ra)) ||
-            (rc = rec(b[r].pb, r, st[r])))
+        if ((rc = sc.up(d.noise, noise, step0, Tr, c0, mc, w_x)) ||
+            (rc = pdhg_slab_trajectories(s[r], &oc, step0, (long long)mc, d.x_in, d.noise, d.x_out, d.rec_x, d.rec_a)) ||
+            (rc = rec(b[r].pb, r, st[r])) ||
+            (rc = sc.down(traj_x, d.rec_x, rx0, step0 + Tr + 1 - rx0, c0, mc, w_x)) ||
+            (rc = sc.down(traj_alp, d.rec_a, step0, Tr, c0, mc, w_a)) ||
+            (r == 0 && (rc = sc.down(x_final, d.x_out, 0, 1, c0, mc, w_x))))
           return rc;
-        for (int j = step0 == 0 ? 0 : step0 + 1; d_rx && j <= step0 + Tr; ++j)
-          HIP_TRY(hipMemcpyAsync(traj_x + ((size_t)j * n + c0) * w_x, d_rx + (size_t)j * mc * w_x,
-                                 mc * w_x * sizeof(double), hipMemcpyDeviceToHost, st[r]));
-        for (int j = step0; d_ra && j < step0 + Tr; ++j)
-          HIP_TRY(hipMemcpyAsync(traj_alp + ((size_t)j * n + c0) * w_a, d_ra + (size_t)j * mc * w_a,
-                                 mc * w_a * sizeof(double), hipMemcpyDeviceToHost, st[r]));
-        if (r == 0 && x_final)
-          HIP_TRY(hipMemcpyAsync(x_final + c0 * w_x, d_out, mc * w_x * sizeof(double), hipMemcpyDeviceToHost, st[r]));
         step0 += Tr;
       }
       if ((rc = full_barrier())) return rc;   // the chunk buffers are reused
     }
     return PDHG_OK;
   }
-  // the staging budgets of the single context (ctx_impl.hpp kReportBudget / kTrajBudget)
-  static constexpr size_t kRowsBudget = Impl<float>::kReportBudget, kSampleBudget = Impl<float>::kTrajBudget;
 
   // total ms between marks [m0, m1) over the recorded steps
   int phase_ms(int m0, int m1, double* ms, int* n) {
@@ -804,17 +764,14 @@ int pdhg_multi_report_state(pdhg_multi* m, pdhg_report* out) {
 }
 int pdhg_multi_report_rows(pdhg_multi* m, int row0, int nrows, double* hj, double* cont) {
   MULTI_GET(m);
-  if (row0 < 0 || nrows < 1) return fail(PDHG_ERR_ARG, "bad row range: row0 %d, nrows %d", row0, nrows);
+  if (int rc = check_row_range(row0, nrows)) return rc;
   return m->report_rows(row0, nrows, hj, cont);
 }
 int pdhg_multi_trajectories(pdhg_multi* m, const pdhg_traj_opts* opts, const double* x_init, const double* noise,
                             double* x_final, double* traj_x, double* traj_alp) {
   MULTI_GET(m);
   if (!opts || !x_init) return fail(PDHG_ERR_ARG, "null opts or x_init");
-  if (opts->n_sample < 1) return fail(PDHG_ERR_ARG, "n_sample must be >= 1");
-  if (opts->sample_offset < 0) return fail(PDHG_ERR_ARG, "sample_offset must be >= 0");
-  if (opts->method != 0 && opts->method != 1) return fail(PDHG_ERR_ARG, "method %d: 0 linear or 1 nearest", opts->method);
-  if (!(opts->x_period > 0) || !(opts->y_period > 0)) return fail(PDHG_ERR_ARG, "periods must be > 0");
+  if (int rc = check_traj_opts(*opts, 2, false)) return rc;   // a multi-device context is always 2-D
   return m->trajectories(*opts, x_init, noise, x_final, traj_x, traj_alp);
 }
 int pdhg_multi_profile(pdhg_multi* m, int enable) {

@@ -1,5 +1,5 @@
 """Compare the gfx950 code of chosen kernels between two builds of libpdhg.so (static check, CPU only).
-usage: python scripts/isa_compare.py OLD_LIB NEW_LIB [symbol-substring ...]
+usage: python scripts/isa_compare.py OLD_LIB NEW_LIB [kernel-name ... | --all]
 
 Every kernel whose symbol contains one of the substrings (default: the kernels that are wrappers around a shared
 body, and their mixed forms) is disassembled from both libraries with the helpers of tests/test_isa_dma.py and
@@ -8,7 +8,9 @@ compared as text after normalisation: addresses, encodings, comments and branch 
   B  the same multiset of opcodes, and the same VGPR / AGPR / SGPR counts, scratch and spill bytes and LDS bytes in
      the code object's metadata (occupancy is a function of these), in another order or on other registers
   C  anything else (the opcodes that differ in number are listed)
-The script knows nothing about particular instructions.  Exit status 1 if a symbol is missing on one side or in C.
+--all takes every symbol of the code objects (a host-only change must leave all of them in tier A) and ends with the
+symbol counts.  The script knows nothing about particular instructions.  Exit status 1 if a symbol is missing on one
+side or in C.
 """
 import collections
 import importlib.util
@@ -67,7 +69,8 @@ def kernels(lib, parts):
         meta = metadata(os.path.join(td, "gfx950.o"))
     out = {}
     for part in parts:
-        for head, body in isa._kernel_bodies(lines, "pdhg" + str(len(part)) + part + "I").items():
+        needle = "" if part == "--all" else "pdhg" + str(len(part)) + part + "I"
+        for head, body in isa._kernel_bodies(lines, needle).items():
             sym = re.search(r"<(.*)>:", head).group(1)
             out[sym] = (normalise(body), meta.get(sym))
     return out
@@ -78,7 +81,7 @@ def main():
     old, new = kernels(old_lib, parts), kernels(new_lib, parts)
     syms = sorted(set(old) | set(new))
     dem = subprocess.run(["c++filt"], input="\n".join(syms), capture_output=True, text=True).stdout.splitlines()
-    bad = 0
+    bad, tiers = 0, collections.Counter()
     print("# tier  instructions old/new  kernel   (metadata: {})".format(" ".join(k.lstrip(".") for k in META)))
     for sym, name in zip(syms, dem):
         name = re.sub(r"^void pdhg::|\(pdhg::KP<.*$", "", name)
@@ -96,7 +99,10 @@ def main():
             diff = {k: (ho[k], hn[k]) for k in sorted(set(ho) | set(hn)) if ho[k] != hn[k]}
             tier, note = "C", "  metadata {} -> {}  opcodes {}".format(" ".join(mo), " ".join(mn), diff)
             bad += 1
+        tiers[tier] += 1
         print("{}  {:>6}/{:<6} {}{}".format(tier, len(bo), len(bn), name, note))
+    if parts == ["--all"]:
+        print("# symbols: old {} new {}; tier A {}, B {}, C {}".format(len(old), len(new), tiers["A"], tiers["B"], tiers["C"]))
     return 1 if bad else 0
 
 

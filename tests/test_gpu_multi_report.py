@@ -248,6 +248,33 @@ def test_row_ranges(native, monkeypatch):
         m.close()
 
 
+def test_row_chunks_inside_a_slab(native, monkeypatch):
+    """(6b): slabs with more rows than one staging chunk holds.  512 x 512 with both fields takes 2 * 512 * 512 * 8 B
+    = 4 MiB per row against the 64 MiB staging budget: 16 rows per chunk, so each 18-row slab of T = 36 over two slabs
+    runs a chunk of 16 rows and one of 2.  The whole window, and a range across the slab boundary (row 18) and a chunk
+    boundary (15 + 16 = 31 lies in slab 1's first chunk [18, 34); slab 0 contributes [15, 18)), against the single
+    context's rows, bit for bit."""
+    _env(monkeypatch, None)
+    egno, epsl = PHYS["e2"]
+    nx = ny = 512
+    T, devs = 36, [0, 0]
+    assert (64 << 20) // (2 * nx * ny * 8) == 16
+    st = _state(egno, 2, nx, ny, T, seed=7)
+    ctx, m = _single(egno, nx, ny, T, "fp32", epsl), _multi(egno, nx, ny, T, "fp32", epsl, devs)
+    try:
+        assert [m.info("rows:%d" % r) for r in range(2)] == [18, 18]      # more than the 16 rows of a chunk
+        ctx.set_state(*st)
+        m.set_state(*st)
+        for r0, n in ((0, T), (15, 20)):
+            hj, cont = ctx.residual_rows(r0, n)
+            h, c = m.residual_rows(r0, n)
+            assert hj.shape == (n, nx, ny) and np.isfinite(hj).all() and np.isfinite(cont).all()
+            assert np.array_equal(h, hj) and np.array_equal(c, cont), (r0, n)
+    finally:
+        ctx.close()
+        m.close()
+
+
 @pytest.mark.parametrize("prec", ["fp32", "fp64"])
 def test_no_side_effects(native, monkeypatch, prec):
     """(7): iterate(2), report + residual_rows + trajectories, iterate(2) ends in the state and the stop statistics
